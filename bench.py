@@ -10,11 +10,17 @@ data-path collective -- DESIGN.md §Multi-GPU).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F]
       (N > 1: the script starts N rank processes itself, one per GPU)
+      a plain run sets up, warms up, times the K steps and prints the line
+  python bench.py --full ...        also the per-stage / roofline figures, the
+      verification against the oracle and the CPU baselines (runs of their own)
+  python bench.py --dump-outputs DIR ...   the last timed step's JFIF streams
+      as DIR/*.npy (dump_jfif), to compare two builds output for output
   torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
 --gpus must equal WORLD_SIZE when a launcher sets it; otherwise bench.py exits
 non-zero instead of reporting a one-GPU number as an N-GPU one.
 
-Rank 0 prints one JSON line (metric, value, roofline, cpu_baseline, ...).
+Rank 0 prints one JSON line (metric, value, ms_per_step, ...; with --full also
+roofline, stages_ms, verified_frames, cpu_baseline, ...).
 """
 from __future__ import annotations
 
@@ -36,6 +42,41 @@ import sharding  # noqa: E402
 import recipes  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: 8.0 TB/s spec
+
+DUMP_WORKLOADS = ("config3", "config4", "regions")   # --dump-outputs: the workloads that end in JFIF streams
+DUMP_SAMPLE_VALUES = 12 << 20                        # jfif_bytes.npy: 48 MiB of float32, under the 64 MB in all
+
+
+def dump_jfif(out_dir, n, output):
+    """--dump-outputs: the n JFIF streams a caller reads back after the last
+    timed step (output(i) -> bytes), as float arrays two builds can be compared by:
+      jfif_len.npy     float64 [n]     byte length of every stream
+      jfif_sum.npy     float64 [n, 2]  per stream: the sum of its bytes, and the sum of
+                                       (position mod 65521 + 1) x byte (integers, exact in float64)
+      jfif_sample.npy  float64 [k]     the streams kept whole: the first k of a seeded
+                                       permutation of 0..n-1 that fit DUMP_SAMPLE_VALUES
+      jfif_bytes.npy   float32 [m]     their bytes, concatenated in that order (the first
+                                       alone and cut to the cap if even it does not fit)"""
+    os.makedirs(out_dir, exist_ok=True)
+    lens, sums = np.zeros(n), np.zeros((n, 2))
+    for i in range(n):
+        b = np.frombuffer(output(i), np.uint8).astype(np.int64)
+        lens[i] = b.size
+        sums[i] = b.sum(), ((np.arange(b.size, dtype=np.int64) % 65521 + 1) * b).sum()
+    room, keep = DUMP_SAMPLE_VALUES, []
+    for i in np.random.default_rng(0).permutation(n):
+        if lens[i] > room:
+            break
+        keep.append(int(i))
+        room -= int(lens[i])
+    if not keep and n:
+        keep = [int(np.random.default_rng(0).permutation(n)[0])]
+    parts = [np.frombuffer(output(i), np.uint8).astype(np.float32) for i in keep]
+    sample = np.concatenate(parts)[:DUMP_SAMPLE_VALUES] if parts else np.zeros(0, np.float32)
+    np.save(os.path.join(out_dir, "jfif_len.npy"), lens)
+    np.save(os.path.join(out_dir, "jfif_sum.npy"), sums)
+    np.save(os.path.join(out_dir, "jfif_sample.npy"), np.asarray(keep, np.float64))
+    np.save(os.path.join(out_dir, "jfif_bytes.npy"), sample)
 
 
 def parse():
@@ -90,7 +131,26 @@ def parse():
                     help="frames re-checked against the oracle after timing (-1: every frame "
                          "of the batch; config3 checks each distinct content with the oracle and "
                          "the reference-build sha256 of tests/golden, then every slot's bytes)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the per-stage and phase "
+                         "passes, roofline and per-kernel figures, the coefficient-variant K1 and "
+                         "PCIe probes, the oracle verification and the CPU baselines (a plain run "
+                         "sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them produced as DIR/<name>.npy "
+                         f"({', '.join(DUMP_WORKLOADS)}: the JFIF byte streams, see dump_jfif)")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run does only what its headline figure needs; say so when an
+        # option of the moved parts was asked for without --full
+        idle = [o for o in ("--verify", "--coef-launches", "--cpu-seconds", "--cpu-workers")
+                if any(a == o or a.startswith(o + "=") for a in sys.argv[1:])]
+        launcher = args.gpus > 1 and "WORLD_SIZE" not in os.environ
+        if idle and not launcher and os.environ.get("RANK", "0") == "0":  # (rank 0 alone says it)
+            print(f"bench.py: {', '.join(idle)} ignored without --full (no verification, CPU baseline "
+                  f"or coefficient-variant launches in a plain run)", file=sys.stderr)
+        args.verify, args.no_cpu_baseline, args.coef_launches = 0, True, 0
+    return args
 
 
 def _free_port() -> int:
@@ -241,10 +301,12 @@ def run_config4(args, world, rank, local, dist):
     band.sync()
     el = time.perf_counter() - t0
     barrier()
+    if args.dump_outputs and rank == 0:  # the root holds the assembled frames
+        dump_jfif(args.dump_outputs, n, full.output)
     # per-phase times of one more step (device protocol: events on the band
     # stream between the phases)
     phases = None
-    if on_dev:
+    if on_dev and args.full:
         import torch
         ev = []
         step(ev)
@@ -349,6 +411,8 @@ def run_regions(args, world, rank, local, dist):
     el = time.perf_counter() - t0
     if dist is not None:
         dist.barrier()
+    if args.dump_outputs and rank == 0:
+        dump_jfif(args.dump_outputs, len(regions), batch.output)
     px = sum(r[2] * r[3] for r in regions)
     el, px_all = sharding.reduce_timing(el, px * args.steps, dist, dist_device(dist, local))
     verified = 0
@@ -445,33 +509,36 @@ def run_detect(args, world, rank, local, dist):
     if dist is not None:
         dist.barrier()
     el, px_all = sharding.reduce_timing(el, W * H * args.steps, dist, dist_device(dist, local))
-    # the detector kernel alone, HIP events on the detector's own stream
-    ds = torch.cuda.ExternalStream(det.stream())
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    reps = 50
-    e0.record(ds)
-    for i in range(reps):
-        det.launch(dframes[i % nf].data_ptr())
-    e1.record(ds)
-    e1.synchronize()
-    k_ms = e0.elapsed_time(e1) / reps
-    sw, sh = W // 4, H // 4
-    k_bytes = 3 * W * H + 2 * 4 * sw * sh + 8 * ((sw + 63) // 64) * sh
-    # verification: the last step's areas and a few JFIFs against the oracle
-    import oracle as O
-    last = (args.warmup + args.steps - 1) % nf
-    prev = O.cref_subsample(frames[(last - 1) % nf])
-    want = O.cref_compare(O.cref_subsample(frames[last]), prev, W, H)
-    got_areas = plan[last]
-    if (len(got_areas), got_areas) != (want[0], want[1]):
-        raise SystemExit("bench detect: areas differ from the oracle")
+    # beside the headline figure (--full): the detector kernel alone and the
+    # verification against the oracle
     verified = 0
-    if args.verify and want[0]:
-        n, areas = want
-        for i in range(n if args.verify < 0 else min(n, 4 * args.verify)):
-            if batch.output(i) != O.cref_encode(frames[last], args.quality, areas[i]):
-                raise SystemExit(f"bench detect: area {i} differs from the oracle")
-            verified += 1
+    if args.full:
+        # the detector kernel alone, HIP events on the detector's own stream
+        ds = torch.cuda.ExternalStream(det.stream())
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        reps = 50
+        e0.record(ds)
+        for i in range(reps):
+            det.launch(dframes[i % nf].data_ptr())
+        e1.record(ds)
+        e1.synchronize()
+        k_ms = e0.elapsed_time(e1) / reps
+        sw, sh = W // 4, H // 4
+        k_bytes = 3 * W * H + 2 * 4 * sw * sh + 8 * ((sw + 63) // 64) * sh
+        # verification: the last step's areas and a few JFIFs against the oracle
+        import oracle as O
+        last = (args.warmup + args.steps - 1) % nf
+        prev = O.cref_subsample(frames[(last - 1) % nf])
+        want = O.cref_compare(O.cref_subsample(frames[last]), prev, W, H)
+        got_areas = plan[last]
+        if (len(got_areas), got_areas) != (want[0], want[1]):
+            raise SystemExit("bench detect: areas differ from the oracle")
+        if args.verify and want[0]:
+            n, areas = want
+            for i in range(n if args.verify < 0 else min(n, 4 * args.verify)):
+                if batch.output(i) != O.cref_encode(frames[last], args.quality, areas[i]):
+                    raise SystemExit(f"bench detect: area {i} differs from the oracle")
+                verified += 1
     res = {
         "metric": "Mpixels/s encoded (device-resident BGR888 -> JFIF bytes)",
         "value": round(px_all / el / 1e6, 1), "unit": "Mpixels/s (frame pixels through detect+encode)",
@@ -485,25 +552,26 @@ def run_detect(args, world, rank, local, dist):
                    "parallelism": f"frame-parallel x{world}"},
         "frames_per_s": round(args.steps * world / el, 1),
         "areas_per_frame": round(nreg / args.steps, 2),
-        "roofline": {"bound": "hbm", "kernel": "k_detect<true> (4x4 subsample + compare + ballot mask)",
-                     "achieved": round(k_bytes / k_ms / 1e6, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(k_bytes / k_ms / 1e6 / HBM_PEAK_GBS, 4), "traffic": None,
-                     "ms_per_launch": round(k_ms, 4), "algorithmic_bytes_per_launch": k_bytes},
         "verified_areas": verified,
     }
-    # PMC-measured HBM bytes of the same kernel on the same workload
-    # (scripts/profile.sh detect -> profiles/rNN/detect/traffic.json)
-    import glob
-    for path in sorted(glob.glob(os.path.join(REPO, "profiles", "r*", "detect", "traffic.json")), reverse=True):
-        d = json.load(open(path))
-        if d.get("config", {}).get("frame") != f"{W}x{H}":
-            continue
-        for name, v in d.get("kernels", {}).items():
-            if "k_detect<true>" in name:
-                res["roofline"]["traffic"] = v["hbm_bytes"]
-                res["roofline"]["traffic_source"] = (f"{os.path.relpath(path, REPO)} (rocprofv3 PMC "
-                                                     f"FETCH_SIZE x2 + WRITE_SIZE, same workload)")
-        break
+    if args.full:
+        res["roofline"] = {"bound": "hbm", "kernel": "k_detect<true> (4x4 subsample + compare + ballot mask)",
+                           "achieved": round(k_bytes / k_ms / 1e6, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(k_bytes / k_ms / 1e6 / HBM_PEAK_GBS, 4), "traffic": None,
+                           "ms_per_launch": round(k_ms, 4), "algorithmic_bytes_per_launch": k_bytes}
+        # PMC-measured HBM bytes of the same kernel on the same workload
+        # (scripts/profile.sh detect -> profiles/rNN/detect/traffic.json)
+        import glob
+        for path in sorted(glob.glob(os.path.join(REPO, "profiles", "r*", "detect", "traffic.json")), reverse=True):
+            d = json.load(open(path))
+            if d.get("config", {}).get("frame") != f"{W}x{H}":
+                continue
+            for name, v in d.get("kernels", {}).items():
+                if "k_detect<true>" in name:
+                    res["roofline"]["traffic"] = v["hbm_bytes"]
+                    res["roofline"]["traffic_source"] = (f"{os.path.relpath(path, REPO)} (rocprofv3 PMC "
+                                                         f"FETCH_SIZE x2 + WRITE_SIZE, same workload)")
+            break
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         use_ref = O.ref_brain_available() and O.ref_available()
         sub_fn = O.ref_subsample if use_ref else O.cref_subsample
@@ -677,24 +745,25 @@ def run_stream(args, world, rank, local, dist):
         }
         # the PCIe ceiling of a host-fed stream: pinned host -> HBM copies of
         # one chunk's bytes (torch on this GPU, after the stream is closed)
-        try:
-            nb = W * H * 3 * args.stream_chunk
-            src = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
-            dst = torch.empty(nb, dtype=torch.uint8, device=f"cuda:{gpu}")
-            dst.copy_(src, non_blocking=True)
-            torch.cuda.synchronize(gpu)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(3):
+        if args.full:
+            try:
+                nb = W * H * 3 * args.stream_chunk
+                src = torch.empty(nb, dtype=torch.uint8, pin_memory=True)
+                dst = torch.empty(nb, dtype=torch.uint8, device=f"cuda:{gpu}")
                 dst.copy_(src, non_blocking=True)
-            e1.record()
-            torch.cuda.synchronize(gpu)
-            h2d = 3 * nb / (e0.elapsed_time(e1) * 1e-3) / 1e9
-            res["pcie_h2d_GB_per_s"] = round(h2d, 1)
-            res["pcie_ceiling_Mpix_s"] = round(h2d * 1e9 / 3 / 1e6, 1)
-            del src, dst
-        except Exception as e:  # noqa: BLE001 (a report field, not the measurement)
-            res["pcie_h2d_GB_per_s"] = f"unmeasured: {e}"
+                torch.cuda.synchronize(gpu)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(3):
+                    dst.copy_(src, non_blocking=True)
+                e1.record()
+                torch.cuda.synchronize(gpu)
+                h2d = 3 * nb / (e0.elapsed_time(e1) * 1e-3) / 1e9
+                res["pcie_h2d_GB_per_s"] = round(h2d, 1)
+                res["pcie_ceiling_Mpix_s"] = round(h2d * 1e9 / 3 / 1e6, 1)
+                del src, dst
+            except Exception as e:  # noqa: BLE001 (a report field, not the measurement)
+                res["pcie_h2d_GB_per_s"] = f"unmeasured: {e}"
         if rank == 0 and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"], par = stream_cpu_baseline(ins[:distinct], outs, W, H, args)
             if par is not None:
@@ -968,6 +1037,9 @@ def main():
         sys.exit(launch_ranks(args))
     if not 1 <= args.quality <= 100:
         raise SystemExit(f"bench.py: --quality {args.quality} outside 1..100")
+    if args.dump_outputs and (args.workload not in DUMP_WORKLOADS or args.mode != "encode"):
+        raise SystemExit(f"bench.py: --dump-outputs writes JFIF streams ({', '.join(DUMP_WORKLOADS)}, "
+                         f"--mode encode), not --workload {args.workload} --mode {args.mode}")
     world, rank, local, dist, torch = dist_setup(args)
     if args.workload == "ranks":
         return run_ranks(args, world, rank, local, dist)
@@ -1004,8 +1076,9 @@ def main():
             dist.barrier()
 
     # the timed steps run without the per-stage events (on a one-frame step
-    # their records are a fifth of the time); the stage breakdown comes from
-    # as many steps again with them, after the timed region
+    # their records are a fifth of the time); with --full the stage breakdown
+    # comes from as many steps again with them, after the timed region
+    # (full_report)
     batch.set_timing(False)
     barrier()
     batch.sync()
@@ -1017,6 +1090,52 @@ def main():
     barrier()
     # max time over ranks, pixels over all ranks (sharding.py; no data-path collective)
     el, px_all = sharding.reduce_timing(el, W * H * F * args.steps, dist, dist_device(dist, local))
+    if args.dump_outputs and rank == 0:
+        dump_jfif(args.dump_outputs, F, batch.output)
+    res = {
+        "metric": "Mpixels/s encoded (device-resident BGR888 -> JFIF bytes)",
+        "value": round(px_all / el / 1e6, 1),
+        "unit": "Mpixels/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(el / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int8-MFMA exact + fp64 replay (bit-exact)",
+        "data": f"synthetic: SURVEY §8(d) config-3 recipe, {args.distinct} distinct frames "
+                f"cycled over the batch",
+        "config": {"workload": f"config 3: {F} x {W}x{H} BGR888 frames per GPU, 4:2:0, "
+                               f"Q={args.quality}, one independent JFIF per frame",
+                   "frames_per_gpu": F, "width": W, "height": H, "quality": args.quality,
+                   "mode": args.mode, "pipeline": "split" if args.split else "fused",
+                   "parallelism": f"frame-parallel x{world}",
+                   **({"options": {k: int(v) for k, v in opts.items()}} if opts else {})},
+        # ranks in the RCCL (nccl backend) process group; 0 for one process or gloo
+        "rccl_world": world if dist is not None and dist.get_backend() == "nccl" else 0,
+        # blocks re-encoded in FP64 by k_fix_blocks (split pipeline) or coefficients
+        # replayed in place (fused pipeline), per frame
+        "fp64_fixups_per_frame": round(batch.replays() / (F * (args.warmup + args.steps)), 2),
+    }
+    if args.full:
+        full_report(args, batch, frames, res, rank, local, dist)
+    if rank == 0:
+        print(json.dumps(res), flush=True)
+    batch.close()
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def full_report(args, batch, frames, res, rank, local, dist):
+    """--full, default workload: what the line carries beside the headline
+    figure, each from runs of its own after the timed region -- the per-stage
+    times, the roofline and per-kernel figures, the coefficient-variant K1
+    and its pattern floor, the verification against the oracle and the
+    reference sha256, and the CPU baselines.  Adds its fields to `res`."""
+    W, H, F = args.width, args.height, args.frames
+    world = res["n_gpus"]
+    run = batch.encode if args.mode == "encode" else batch.dct
 
     batch.set_timing(True)
     for _ in range(args.steps):
@@ -1063,7 +1182,6 @@ def main():
     # per-rank verification counts (every rank checks its own batch)
     ver_ranks = sharding.gather_ints([verified, pinned], dist, dist_device(dist, local))
     px_step = W * H * F
-    value = px_all / el / 1e6
     geo = batch.geometry()
     # algorithmic HBM bytes per launch (DESIGN.md "Roofline accounting"):
     # BGR in 3 B/px; coefficient planes 2 B x 64 per block (= 3 B/px at 4:2:0);
@@ -1084,26 +1202,7 @@ def main():
     dom = max(kernels, key=lambda k: kernels[k][1])
     k1_bytes, dom_ms, dom_desc = kernels[dom]
     k1_gbs = k1_bytes / (dom_ms * 1e-3) / 1e9
-    res = {
-        "metric": "Mpixels/s encoded (device-resident BGR888 -> JFIF bytes)",
-        "value": round(value, 1),
-        "unit": "Mpixels/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(el / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "int8-MFMA exact + fp64 replay (bit-exact)",
-        "data": f"synthetic: SURVEY §8(d) config-3 recipe, {args.distinct} distinct frames "
-                f"cycled over the batch",
-        "config": {"workload": f"config 3: {F} x {W}x{H} BGR888 frames per GPU, 4:2:0, "
-                               f"Q={args.quality}, one independent JFIF per frame",
-                   "frames_per_gpu": F, "width": W, "height": H, "quality": args.quality,
-                   "mode": args.mode, "pipeline": "split" if args.split else "fused",
-                   "parallelism": f"frame-parallel x{world}",
-                   **({"options": {k: int(v) for k, v in opts.items()}} if opts else {})},
+    res.update({
         "roofline": {"bound": "hbm", "kernel": f"{dom} ({dom_desc})",
                      "achieved": round(k1_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(k1_gbs / HBM_PEAK_GBS, 4), "traffic": None,
@@ -1119,12 +1218,9 @@ def main():
         "verified_frames": verified,
         "verified_contents_pinned_to_reference_sha": pinned,
         "verified_frames_per_rank": [v[0] for v in ver_ranks],
-        # ranks in the RCCL (nccl backend) process group; 0 for one process or gloo
-        "rccl_world": world if dist is not None and dist.get_backend() == "nccl" else 0,
-        # blocks re-encoded in FP64 by k_fix_blocks (split pipeline) or coefficients
-        # replayed in place (fused pipeline), per frame
-        "fp64_fixups_per_frame": round(replays / (F * (args.warmup + 2 * args.steps)), 2),  # timed + events pass
-    }
+        # the timed steps and the events pass
+        "fp64_fixups_per_frame": round(replays / (F * (args.warmup + 2 * args.steps)), 2),
+    })
     if coef_ms is not None:
         cb = px_step * 3 + coef_bytes + dc_bytes
         res["roofline_k1_coefficient_variant"] = {
@@ -1155,11 +1251,6 @@ def main():
         if args.cpu_workers > 1:
             res["cpu_baseline_parallel"] = cpu_baseline_parallel(H, W, args.cpu_seconds,
                                                                  args.cpu_workers)
-    if rank == 0:
-        print(json.dumps(res), flush=True)
-    batch.close()
-    if dist is not None:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

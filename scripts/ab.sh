@@ -6,6 +6,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 # (ENVS="A=0 A=1" instead of LIBS: the in-tree library under each setting)
+ARGS="--full ${ARGS:-}"  # the per-stage times and the coefficient K1 are behind --full
 for r in $(seq ${ROUNDS:-3}); do
   for lib in ${ENVS:-$LIBS}; do
     if [ -n "${ENVS:-}" ]; then setting=$lib; else setting=MIJ_LIB=$PWD/$lib; fi

@@ -4,6 +4,7 @@
 # HIP events.  Usage: LIBS="ab/A.so ab/B.so" [ROUNDS=2] bash scripts/ab_coef.sh
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
+ARGS="--full ${ARGS:-}"  # the coefficient launches are behind --full
 for r in $(seq ${ROUNDS:-2}); do
   for lib in $LIBS; do
     MIJ_LIB=$PWD/$lib timeout -k 10 300 python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --verify 0 --coef-launches 5 ${ARGS:-} > gpurun_out/ab_coef.log 2>&1 || { echo "$lib failed"; tail -5 gpurun_out/ab_coef.log; exit 1; }

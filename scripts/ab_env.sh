@@ -3,6 +3,7 @@
 # pairs in one GPU session (ab/libmijpeg_LIB.so, or LIB=cur for the in-tree build)
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
+ARGS="--full ${ARGS:-}"  # the per-stage times are behind --full
 for r in $(seq ${ROUNDS:-2}); do
 for v in "$@"; do
   lib=${v%%:*}; ev=${v#*:}

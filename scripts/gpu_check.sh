@@ -8,6 +8,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 170 --timeout
 tail -3 gpurun_out/pytest_gpu.log
 [ $rc -eq 0 ] || { grep -E "Error|assert|FAILED" gpurun_out/pytest_gpu.log | head -20; exit $rc; }
 [ -n "${NO_BENCH:-}" ] && exit 0
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the verification of every slot is behind --full
 timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > gpurun_out/bench.log 2>&1 || { tail -5 gpurun_out/bench.log; exit 1; }
 tail -1 gpurun_out/bench.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1 || { tail -5 gpurun_out/smoke.log; exit 1; }

@@ -13,6 +13,6 @@ step() {
   if [ $rc -ne 0 ]; then echo "stopping after $name (rc=$rc)"; exit $rc; fi
 }
 step pytest_decode 600 python -u -m pytest tests/test_decode.py -m gpu -x -q --timeout 120 --timeout-method thread
-step bench_decode 300 python bench.py --workload decode --steps 3 --warmup 1
+step bench_decode 300 python bench.py --full --workload decode --steps 3 --warmup 1
 step prof_decode 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/decode/prof -o run -- python bench.py --workload decode --steps 3 --warmup 1
 find gpurun_out/decode/prof -name '*kernel_stats.csv' -exec cat {} \;

@@ -8,7 +8,7 @@ out=gpurun_out/final_${1:-r04}; mkdir -p $out
 export TMPDIR=/tmp
 run() {
   local name=$1 secs=$2; shift 2
-  timeout -k 10 $secs python3 bench.py "$@" > $out/$name.log 2>&1 || { echo "$name failed"; tail -5 $out/$name.log; exit 1; }
+  timeout -k 10 $secs python3 bench.py --full "$@" > $out/$name.log 2>&1 || { echo "$name failed"; tail -5 $out/$name.log; exit 1; }
   grep '^{' $out/$name.log | tail -1 > $out/$name.json
   python3 -c "import json,sys;d=json.load(open('$out/$name.json'));print(sys.argv[1], d['ms_per_step'], d['value'], d.get('stages_ms') or d.get('phases_ms'), d.get('verified_frames', d.get('verified_files')))" $name
 }

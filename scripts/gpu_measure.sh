@@ -11,7 +11,7 @@ out=gpurun_out/meas; mkdir -p $out
 export TMPDIR=/tmp
 run() {  # name seconds args...
   local name=$1 secs=$2; shift 2
-  timeout -k 10 "$secs" python3 bench.py "$@" > $out/$name.log 2>&1 || { echo "$name failed rc=$?"; tail -5 $out/$name.log; exit 1; }
+  timeout -k 10 "$secs" python3 bench.py --full "$@" > $out/$name.log 2>&1 || { echo "$name failed rc=$?"; tail -5 $out/$name.log; exit 1; }
   grep '^{' $out/$name.log | tail -1 > $out/$name.json
   python3 - "$name" "$out/$name.json" <<'P'
 import json, sys

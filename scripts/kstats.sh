@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 out=gpurun_out/kstats_$tag
 mkdir -p "$out"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -o run -- \
-  python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --verify 0 "$@" > "$out/bench.log" 2>&1 || { tail -5 "$out/bench.log"; exit 1; }
+  python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --verify 0 "$@" > "$out/bench.log" 2>&1 || { tail -5 "$out/bench.log"; exit 1; }
 python3 - "$out" <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/run_kernel_stats.csv", recursive=True)[0]

@@ -11,7 +11,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 out=gpurun_out/util_$tag
 mkdir -p "$out"
-ARGS="--steps 2 --warmup 1 --verify 0 --no-cpu-baseline --coef-launches 2 ${BENCH_ARGS:-}"
+ARGS="--full --steps 2 --warmup 1 --verify 0 --no-cpu-baseline --coef-launches 2 ${BENCH_ARGS:-}"
 i=0
 while read -r grp; do
   [ -z "$grp" ] && continue

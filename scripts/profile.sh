@@ -16,8 +16,8 @@ run() {
   echo "== $name rc=$rc"; tail -n 3 "$out/$name.log"
   [ $rc -eq 0 ] || { echo "stopping after $name"; exit $rc; }
 }
-ARGS="--no-cpu-baseline ${BENCH_ARGS:-}"
-run bench_plain 600 python3 bench.py ${BENCH_ARGS:-}
+ARGS="--full --no-cpu-baseline ${BENCH_ARGS:-}"
+run bench_plain 600 python3 bench.py --full ${BENCH_ARGS:-}
 run stats 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o run -- \
     python3 bench.py $ARGS
 run pmc_fetch 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -o run -- \

@@ -5,11 +5,11 @@
 # alternating (MIJ_LIB); otherwise the in-tree library with and without
 # option $OPT (default segdc_fused=1).
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+out=${OUT_DIR:-bench_out}; mkdir -p $out  # logs (OUT_DIR: where to keep them)
 OPT=${OPT:-segdc_fused=1}
 run() {  # <label> <env-or-empty> <extra args>
-  env $2 timeout -k 10 120 python3 bench.py --frames $n --width 1920 --height 1280 --steps 200 --warmup 20 --no-cpu-baseline --coef-launches 0 --verify 0 $3 > gpurun_out/sb.log 2>&1 || { echo "failed: n=$n $1"; tail -5 gpurun_out/sb.log; exit 1; }
-  python3 -c "import json,sys;d=json.loads(open('gpurun_out/sb.log').read().strip().splitlines()[-1]);s=d['stages_ms'];print('n', sys.argv[1], sys.argv[2], round(d['ms_per_step'],4), {k: s[k] for k in s})" $n "$1"
+  env $2 timeout -k 10 120 python3 bench.py --full --frames $n --width 1920 --height 1280 --steps 200 --warmup 20 --no-cpu-baseline --coef-launches 0 --verify 0 $3 > $out/sb.log 2>&1 || { echo "failed: n=$n $1"; tail -5 $out/sb.log; exit 1; }
+  python3 -c "import json,sys;d=json.loads(open('$out/sb.log').read().strip().splitlines()[-1]);s=d['stages_ms'];print('n', sys.argv[1], sys.argv[2], round(d['ms_per_step'],4), {k: s[k] for k in s})" $n "$1"
 }
 for n in ${NS:-1 4 16}; do
   for r in $(seq ${ROUNDS:-2}); do

@@ -57,6 +57,16 @@ def test_one_gpu_needs_no_process_group():
     assert res["n_gpus"] == 1 and res["backend"] == "none" and res["ranks"] == [0]
 
 
+def test_options_of_the_full_run_are_named_when_ignored():
+    # --verify / --coef-launches / --cpu-seconds act only with --full; a plain
+    # run says once that it ignores them, a --full run says nothing
+    r = _bench(["--gpus", "2", "--workload", "ranks", "--verify", "4", "--cpu-seconds=1"], _env())
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stderr.count("--verify, --cpu-seconds ignored without --full") == 1, r.stderr
+    r = _bench(["--gpus", "1", "--workload", "ranks", "--verify", "4", "--full"], _env())
+    assert r.returncode == 0 and "ignored without --full" not in r.stderr, r.stderr
+
+
 def test_failing_rank_fails_the_launch():
     # ranks that reject their arguments end the launch with a non-zero
     # code, and the parent prints no line of its own

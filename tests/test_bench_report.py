@@ -38,6 +38,37 @@ def test_util_counters_require_matching_workload(tmp_path, monkeypatch):
     assert b.util_counters("k_mcu_dct<2>", dict(cfg)) == (None, None)
 
 
+def test_dump_jfif_is_float_deterministic_and_capped(tmp_path, monkeypatch):
+    """--dump-outputs: every stream's length and checksums, and whole streams
+    of a seeded sample as float32 under the cap; the same streams give the
+    same files."""
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(5)
+    streams = [rng.integers(0, 256, size=int(n), dtype=np.uint8).tobytes()
+               for n in rng.integers(1, 4000, size=12)]
+    monkeypatch.setattr(b, "DUMP_SAMPLE_VALUES", 6000)
+    for d in ("a", "b"):
+        b.dump_jfif(str(tmp_path / d), len(streams), lambda i: streams[i])
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["jfif_bytes", "jfif_len", "jfif_sample", "jfif_sum"]
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert got["jfif_len"].tolist() == [len(s) for s in streams]
+    assert got["jfif_sum"][:, 0].tolist() == [sum(s) for s in streams]
+    assert got["jfif_sum"][3, 1] == sum((p + 1) * v for p, v in enumerate(streams[3]))
+    keep = [int(i) for i in got["jfif_sample"]]
+    assert keep and len(set(keep)) == len(keep)
+    assert got["jfif_bytes"].size <= 6000
+    assert got["jfif_bytes"].astype(np.uint8).tobytes() == b"".join(streams[i] for i in keep)
+    for name, v in got.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{name}.npy")), name
+    # a first stream longer than the cap is cut to it, not dropped
+    monkeypatch.setattr(b, "DUMP_SAMPLE_VALUES", 10)
+    b.dump_jfif(str(tmp_path / "c"), len(streams), lambda i: streams[i])
+    assert np.load(tmp_path / "c" / "jfif_bytes.npy").size == min(10, len(streams[int(np.load(
+        tmp_path / "c" / "jfif_sample.npy")[0])]))
+
+
 def test_committed_profiles_attach_to_the_default_bench():
     """The newest committed util.json and traffic.json record the workload
     they were measured on, and it is the default bench's (config 3), so the

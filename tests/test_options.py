@@ -6,7 +6,7 @@ A config-3-sized batch takes paths no small batch reaches (mij_api.hip
 ent_args / run_entropy): 48 JFIF-assembly slots per frame at >= 43 frames
 and Q <= 60, the AC tables built beside the segment DCs (k_segdc_actab) plus
 DC-only tables at >= 16 frames, and the histogram / pack-state fills the
-next encode skips after them.  bench.py verifies its own run; these tests
+next encode skips after them.  bench.py --full verifies its own run; these tests
 pin the same paths in the GPU suite, at frame counts that move across the
 thresholds in both directions.  Then every MIJ_OPT_* setting other than the
 default, which the bench never runs, must give the same bytes."""
