@@ -384,6 +384,7 @@ struct mij_batch {
   hipEvent_t *ev = evh[0];       // current step's events
   long long steps = 0;
   int last_frames = 0;
+  int plan[MIJ_PLAN_FIELDS] = {};  // mij_test_last_plan (csrc/mij_testing.h): the last encode's launch plan
 };
 
 template <class T>
@@ -394,7 +395,14 @@ static hipError_t dalloc(T **p, size_t count) {
 static void batch_free(mij_batch *b) {
   if (!b) return;
   hipSetDevice(b->dev);
-  if (b->stream && b->stream != b->own_stream) hipStreamSynchronize(b->stream);
+  if (b->own_stream && b->stream != b->own_stream) {
+    // still switched to a caller's stream (mij_batch_set_stream): the batch's
+    // own stream waits for what was enqueued there and the batch goes back to
+    // it, so the caller's handle is not used again below
+    if (b->stream && b->ev_switch && hipEventRecord(b->ev_switch, b->stream) == hipSuccess)
+      hipStreamWaitEvent(b->own_stream, b->ev_switch, 0);
+    b->stream = b->own_stream;
+  }
   if (b->own_stream) hipStreamSynchronize(b->own_stream);
   void *ptrs[] = {b->d_tab, b->own_in ? b->d_in : nullptr, b->d_coef, b->d_dc, b->d_hist,
                   b->d_ehuf, b->d_raw, b->d_tok, b->d_tok0, b->d_seg_ntok, b->d_seg_bits, b->d_seg_off,
@@ -547,6 +555,11 @@ extern "C" int mij_batch_set_stream(mij_batch *b, void *stream) {
   HIP_TRY(hipSetDevice(b->dev));
   const hipStream_t s = stream ? (hipStream_t)stream : b->own_stream;
   if (s == b->stream) return MIJ_OK;
+  if (s != b->own_stream) {  // a caller's stream: it must belong to the batch's device
+    hipDevice_t sdev, bdev;
+    if (hipStreamGetDevice(s, &sdev) != hipSuccess || hipDeviceGet(&bdev, b->dev) != hipSuccess || sdev != bdev)
+      return fail(MIJ_EINVAL, "set_stream: not a stream of the batch's device %d", b->dev);
+  }
   // the new stream runs after everything enqueued so far on the old one
   if (!b->ev_switch) HIP_TRY(hipEventCreateWithFlags(&b->ev_switch, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(b->ev_switch, b->stream));
@@ -689,6 +702,10 @@ static EntArgs ent_args(mij_batch *b, int nframes, int f0 = 0, bool band = false
                                                                 : 192;
   a.pack_wide = ent_args_pack_wide(b);
   ent_args_pack_ls(b, nframes, a.pack_ls);
+  b->plan[MIJ_PLAN_EMIT_SLOTS] = a.emit_slots;
+  b->plan[MIJ_PLAN_PACK_WIDE] = a.pack_wide;
+  b->plan[MIJ_PLAN_PACK_LS_LUMA] = a.pack_ls[0];
+  b->plan[MIJ_PLAN_PACK_LS_CHROMA] = a.pack_ls[1];
   if (f0) {  // sub-batch: frames f0.. of the batch (every per-frame array shifted)
     const Geom &g = b->g;
     const long long F = f0, gpf = pack_stride(g);
@@ -784,6 +801,7 @@ static int run_k1(mij_batch *b, int nframes, int mode, int dc_diffed = 0, int se
     HIP_TRY(hipMemsetAsync(d_wt, 0, sizeof(unsigned long long) * K1_WTIME_WORDS * nw, b->stream));
     k.wtime = d_wt;
   }
+  b->plan[MIJ_PLAN_K1_MODE] = mode;
   HIP_TRY(launch_k1(k, (int)grid, mode, b->stream));
   if (d_wt) {
     const int WW = K1_WTIME_WORDS;
@@ -826,6 +844,11 @@ static int run_entropy(mij_batch *b, int nframes, bool dc_fix, bool tables_given
                        hipStream_t st = nullptr) {
   b->band_hist_zero = 0;  // (its segment DCs add onto d_hist)
   EntArgs a = ent_args(b, nframes, f0);
+  int *const plan = b->plan;
+  plan[MIJ_PLAN_NFRAMES] = nframes;
+  plan[MIJ_PLAN_F0] = f0;
+  plan[MIJ_PLAN_ENTROPY_CALLS]++;
+  plan[MIJ_PLAN_TABLES] = 0;
   const bool t = b->timing && !st;  // (sub-batches: no stage events)
   if (!st) st = b->stream;
   // segment-first DC tokens: inside k_tables (its DC-table waves), or on
@@ -857,16 +880,23 @@ static int run_entropy(mij_batch *b, int nframes, bool dc_fix, bool tables_given
     static const int dc_last_nozero = diag_env("MIJ_DC_LAST_NOZERO", 0);  // (diag: the packing zeroes its state)
     a.zero_pack = dc_last && dc_last_nozero ? 0 : 1;  // (the AC workgroups zero the counts they read)
     a.dc_last = dc_last;
+    plan[MIJ_PLAN_SEGDC] = 2;
     HIP_TRY(launch_segdc_actab(a, st));
   } else if (dc_fix && !a.seg_dc) {
+    plan[MIJ_PLAN_SEGDC] = 1;
     HIP_TRY(launch_seg_dc(a, st));
+  } else {
+    plan[MIJ_PLAN_SEGDC] = a.seg_dc ? 3 : 0;
   }
+  plan[MIJ_PLAN_DC_LAST] = a.dc_last;
+  plan[MIJ_PLAN_ACTAB] = actab;
   if (t) HIP_TRY(hipEventRecord(b->ev[4], st));
   if (!tables_given && ttime) {
     EntArgs at = a;
     const size_t nt = (size_t)nframes * 4 * 10;
     HIP_TRY(hipMalloc(&at.dbg, sizeof(unsigned long long) * nt));
     HIP_TRY(hipMemsetAsync(at.dbg, 0, sizeof(unsigned long long) * nt, st));
+    plan[MIJ_PLAN_TABLES] = 4;
     HIP_TRY(launch_tables(at, st));
     std::vector<unsigned long long> h(nt);
     HIP_TRY(hipMemcpyAsync(h.data(), at.dbg, sizeof(unsigned long long) * nt, hipMemcpyDeviceToHost, st));
@@ -930,6 +960,7 @@ static int run_entropy(mij_batch *b, int nframes, bool dc_fix, bool tables_given
   } else if (!tables_given && !dc_last) {
     a.zero_pack = !a.seg_dc;  // one wave per table: it zeroes the pack state too
     a.tab_dc_only = actab;
+    plan[MIJ_PLAN_TABLES] = a.tab_dc_only ? 2 : 4;
     HIP_TRY(launch_tables(a, st));
     a.tab_dc_only = 0;
   }
@@ -976,6 +1007,9 @@ static int run_entropy(mij_batch *b, int nframes, bool dc_fix, bool tables_given
   // 0.073 ms with the error words zeroed by K1; at config 3 the per-frame
   // serial fixes cost emit ~20 us, more than the launch)
   a.seam_in_scan = a.seam && a.ff_pack && nframes < 16;
+  plan[MIJ_PLAN_SEAM] = a.seam != nullptr;
+  plan[MIJ_PLAN_FF_PACK] = a.ff_pack;
+  plan[MIJ_PLAN_SEAM_IN_SCAN] = a.seam_in_scan;
   if (a.seam && !a.seam_in_scan) HIP_TRY(launch_seam_fix(a, st));
   if (ptime) {
     std::vector<unsigned long long> h(6 * nwords);
@@ -1016,6 +1050,8 @@ static int run_entropy(mij_batch *b, int nframes, bool dc_fix, bool tables_given
 }
 
 static int encode_frames(mij_batch *b, int nframes) {
+  b->plan[MIJ_PLAN_ENTROPY_CALLS] = 0;
+  b->plan[MIJ_PLAN_HIST_FILL_SKIPPED] = nframes <= b->hist_zero_n;
   if (nframes > b->hist_zero_n)
     HIP_TRY(hipMemsetAsync(b->d_hist, 0, sizeof(uint32_t) * nframes * 4 * 257, b->stream));
   b->hist_zero_n = 0;
@@ -1678,6 +1714,20 @@ extern "C" int mij_encode_regions(const uint8_t *bgr, int stride_px, int frame_h
   }
   HIP_TRY(hipStreamSynchronize(b->stream));
   return MIJ_OK;
+}
+
+// test-only (csrc/mij_testing.h): the launch plan the last encode stored;
+// b == NULL: the region context's (mij_encode_regions)
+extern "C" int mij_test_last_plan(mij_batch *b, int *out, int n) {
+  if (!out || n < 0) return fail(MIJ_EINVAL, "test_last_plan: bad args"), -2;
+  std::unique_lock<std::mutex> l(g_mu, std::defer_lock);
+  if (!b) {
+    l.lock();
+    b = g_rctx;
+  }
+  if (!b) return fail(MIJ_EINVAL, "test_last_plan: no batch"), -2;
+  for (int i = 0; i < n && i < MIJ_PLAN_FIELDS; i++) out[i] = b->plan[i];
+  return MIJ_PLAN_FIELDS;
 }
 
 // ---------------------------------------------------------------------------

@@ -74,6 +74,12 @@ OPTIONS = {"seam": 0, "ff_pack": 1, "actab": 2, "segdc_fused": 3, "pack_wide": 4
            "overlap_prio": 6, "pack_segs": 8}
 
 
+# mij_test_last_plan (csrc/mij_testing.h: MIJ_PLAN_*), in the library's order
+PLAN_FIELDS = ["nframes", "f0", "entropy_calls", "dc_last", "actab", "tables", "segdc", "seam", "ff_pack",
+               "seam_in_scan", "emit_slots", "pack_ls_luma", "pack_ls_chroma", "pack_wide",
+               "hist_fill_skipped", "k1_mode"]
+
+
 _lib = None
 
 
@@ -299,6 +305,23 @@ def encode_regions(frame_bgr: np.ndarray, regions, quality: int = 50) -> list:
     return res
 
 
+def _last_plan(handle) -> dict:
+    """mij_test_last_plan (test-only, csrc/mij_testing.h; bound by name): the
+    launch plan the last encode stored, as {field: value}."""
+    fn = load().mij_test_last_plan
+    fn.argtypes, fn.restype = [C.c_void_p, C.POINTER(C.c_int), C.c_int], C.c_int
+    out = (C.c_int * len(PLAN_FIELDS))()
+    n = fn(handle, out, len(PLAN_FIELDS))
+    if n != len(PLAN_FIELDS):  # -2: bad arguments; anything else: this list is out of date
+        raise MijError(f"mij_test_last_plan: {n} fields, expected {len(PLAN_FIELDS)}")
+    return dict(zip(PLAN_FIELDS, [int(v) for v in out]))
+
+
+def regions_last_plan() -> dict:
+    """the launch plan of the last encode_regions call"""
+    return _last_plan(None)
+
+
 def encode(frame_bgr: np.ndarray, quality: int = 50, region=None) -> bytes:
     """mij_encode: whole path host->host."""
     lib = load()
@@ -404,6 +427,11 @@ class Batch:
 
     def encode(self, n: int) -> None:
         _check(self.lib.mij_batch_encode(self.h_, n), "encode")
+
+    def last_plan(self) -> dict:
+        """what the last encode() launched (PLAN_FIELDS): host state the
+        encode stored as it decided, read without touching the device"""
+        return _last_plan(self.h_)
 
     def dct(self, n: int) -> None:
         _check(self.lib.mij_batch_dct(self.h_, n), "dct")

@@ -118,3 +118,92 @@ def test_repeated_encodes_growing_and_shrinking_frame_counts():
     b.encode(2)
     assert [b.output(i) for i in range(2)] == want[:2]
     b.close()
+
+
+def _set_stream_body():
+    # torch's HIP runtime first: it does not initialise after the library's
+    # in one process (tests/test_bands.py _nccl_rank)
+    import torch
+    torch.cuda.set_device(0)
+    W, H, n = 256, 128, 3
+    frames = np.stack([recipes.config3_frame(30, H, W), recipes.noise(H, W, 31), recipes.near_gray(H, W, 32)])
+    want = [O.cref_encode(f) for f in frames]
+    plan = dict(nframes=n, f0=0, entropy_calls=1, dc_last=1, tables=0, seam_in_scan=1, k1_mode=2)
+
+    def encode_and_check(b, what):
+        b.encode(n)
+        p = b.last_plan()
+        assert {k: p[k] for k in plan} == plan, p
+        assert [b.output(i) for i in range(n)] == want, what
+
+    ts = torch.cuda.Stream()
+    foreign = int(ts.cuda_stream)
+    b = mijpeg.Batch(W, H, n)
+    b2 = mijpeg.Batch(W, H, n)
+    try:
+        own = b.stream_ptr()
+        assert own and foreign and own != foreign
+        b.upload(frames)
+        encode_and_check(b, "own stream")
+        b.set_stream(own)  # the stream in use: nothing changes
+        assert b.stream_ptr() == own
+        b.set_stream(foreign)
+        assert b.stream_ptr() == foreign
+        b.set_stream(foreign)
+        assert b.stream_ptr() == foreign
+        encode_and_check(b, "torch stream")
+        b.set_stream(0)
+        assert b.stream_ptr() == own
+        b.set_stream(0)
+        assert b.stream_ptr() == own
+        encode_and_check(b, "own stream again")
+        if torch.cuda.device_count() > 1:  # a stream of another device is refused
+            other = torch.cuda.Stream(device=1)
+            with pytest.raises(mijpeg.MijError, match="not a stream of the batch's device"):
+                b.set_stream(int(other.cuda_stream))
+            assert b.lib.mij_last_error() == 1  # MIJ_EINVAL
+            assert b.stream_ptr() == own
+        # closed while switched, work still queued on the torch stream
+        own2 = b2.stream_ptr()
+        b2.upload(frames)
+        b2.set_stream(foreign)
+        encode_and_check(b2, "second batch, torch stream")
+        b2.encode(n)
+        assert b2.stream_ptr() == foreign and own2 != foreign
+    finally:
+        b2.close()
+        b.close()
+    # the torch stream is still usable after the close
+    with torch.cuda.stream(ts):
+        x = torch.arange(1024, device="cuda", dtype=torch.int64).sum()
+    ts.synchronize()
+    assert int(x) == 1024 * 1023 // 2
+
+
+def _set_stream_proc(q):
+    import traceback
+    try:
+        _set_stream_body()
+        q.put("ok")
+    except BaseException:
+        q.put(traceback.format_exc())
+        raise
+
+
+def test_set_stream_switch_back_and_close_while_switched():
+    """mij_batch_set_stream: the batch's own stream, a torch stream's handle,
+    the own stream again (0) -- the oracle's bytes after each step, and
+    mij_batch_stream names the stream in use; switching to the current stream
+    changes nothing.  A second batch is then closed while still switched, the
+    torch stream alive: its own stream waits for the work enqueued there and
+    the close does not use the caller's handle afterwards.  In
+    a fresh process, where torch's HIP runtime can start first."""
+    import multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    p = ctx.Process(target=_set_stream_proc, args=(q,))
+    p.start()
+    got = q.get(timeout=300)
+    p.join(timeout=120)
+    assert got == "ok", got
+    assert p.exitcode == 0

@@ -99,21 +99,30 @@ def test_decode_quality_sweep_and_long_codes(quality):
 
 
 @pytest.mark.gpu
-def test_repeated_encodes_same_bytes_small_batch():
+def test_repeated_encodes_same_bytes_small_batch(manifest):
     """The same two-frame batch (config-3 frame + uniform noise, the
     small-batch paths: seam fixes inside k_emit_scan, DC tables inside the
-    segment-DC launch) encoded 12 times: identical JFIF bytes every time, and
-    each decodes to the encoder's own coefficients.  (Round 6: a missing
-    barrier between the seam fixes and the chunk-count reads made the noise
-    frame's bytes differ in about a third of the repetitions.)"""
+    segment-DC launch -- asserted from the plan) encoded 12 times: every
+    repetition's bytes are the oracle's (the config-3 frame's also the
+    reference build's sha), identical every time, and the first decodes to
+    the encoder's own coefficients.  (Round 6: a missing barrier between the
+    seam fixes and the chunk-count reads made the noise frame's bytes differ
+    in about a third of the repetitions.)"""
     frames = np.stack([recipes.config3_frame(0), recipes.config3_uniform(1)])
+    want = [O.cref_encode(f) for f in frames]
+    want_shas = [hashlib.sha256(x).hexdigest() for x in want]
+    assert want_shas[0] == manifest["config3_frame0"]["jpg_sha256"]
+    plan = dict(nframes=2, entropy_calls=1, seam=1, ff_pack=1, seam_in_scan=1, dc_last=1, actab=1, tables=0,
+                segdc=2, k1_mode=3)
     b = mijpeg.Batch(3840, 2160, 2, 50, keep_coefs=True)
     d = mijpeg.Decoder(3840, 2160, 2)
     try:
         b.upload(frames)
         first = None
-        for _ in range(12):
+        for rep in range(12):
             b.encode(2)
+            p = b.last_plan()
+            assert {k: p[k] for k in plan} == plan, p
             streams = [b.output(i) for i in range(2)]
             shas = [hashlib.sha256(x).hexdigest() for x in streams]
             if first is None:
@@ -122,10 +131,40 @@ def test_repeated_encodes_same_bytes_small_batch():
                 for i in range(2):
                     for g, w in zip(d.coefs(i), b.coefs(i, diffed=True)):
                         assert (g == w).all()
-            assert shas == first
+            assert shas == first, rep
+            assert streams == want, rep
     finally:
         b.close()
         d.close()
+
+
+@pytest.mark.gpu
+def test_repeated_encodes_seam_in_scan_batch_vs_oracle():
+    """The largest batch whose seams k_emit_scan fixes itself: 15 frames of
+    496x272 (the last pack group of each scan short, two segment-DC
+    workgroups per frame), two of them noise, encoded 6 times; the plan and
+    every repetition's bytes against the oracle.  A determinism check of
+    correct code: the first difference fails the test."""
+    h, w, n = 272, 496, 15
+    kinds = [recipes.config3_frame(50 + i, h, w) for i in range(n)]
+    kinds[4], kinds[11] = recipes.noise(h, w, 61), recipes.noise(h, w, 62)
+    kinds[7] = recipes.near_gray(h, w, 63)
+    frames = np.stack(kinds)
+    want = [O.cref_encode(f) for f in frames]
+    plan = dict(nframes=n, entropy_calls=1, seam=1, ff_pack=1, seam_in_scan=1, dc_last=1, actab=1, tables=0,
+                segdc=2, emit_slots=192, k1_mode=2)
+    b = mijpeg.Batch(w, h, n)
+    try:
+        b.upload(frames)
+        for rep in range(6):
+            b.encode(n)
+            p = b.last_plan()
+            assert {k: p[k] for k in plan} == plan, p
+            assert p["hist_fill_skipped"] == int(rep > 0)
+            for i in range(n):
+                assert b.output(i) == want[i], (rep, i)
+    finally:
+        b.close()
 
 
 @pytest.mark.gpu
