@@ -490,6 +490,38 @@ int mij_decoder_passes(mij_decoder *d);
 /* device address of stream `frame`'s planes (Y, then Cb, then Cr) */
 void *mij_decoder_device_coefs(mij_decoder *d, int frame);
 
+/* ---- decode to pixels -------------------------------------------------------
+ * The decoded coefficients through libjpeg's integer ("islow") IDCT, its h2v2
+ * "fancy" chroma upsampling and its fixed-point colour conversion, on the
+ * GPU: on the streams libjpeg decodes correctly the pixels are libjpeg's byte
+ * for byte (DESIGN.md "Decode to pixels" states the arithmetic and the one
+ * kind of stream on which the two differ). */
+enum { MIJ_PIX_BGR = 0, MIJ_PIX_RGB = 1 };
+/* all frames of the last mij_decoder_decode -> planes and pixels; async on
+ * the decoder's stream; buffers allocated on first use, so a decoder used
+ * only as verifier costs what it costs without this call */
+int mij_decoder_reconstruct(mij_decoder *d, int order);
+/* host copy of frame's w*h pixels, rows pitch bytes apart (0 = 3*w; the bytes
+ * between rows are not written); waits */
+int mij_decoder_pixels(mij_decoder *d, int frame, uint8_t *dst, size_t cap, long long pitch);
+/* the IDCT output before upsampling: Y[w*h], Cb[w*h/4], Cr[w*h/4] */
+int mij_decoder_planes(mij_decoder *d, int frame, uint8_t *Y, uint8_t *Cb, uint8_t *Cr);
+/* device address of frame's pixels, packed rows (*pitch = 3*w, a multiple of
+ * 16: usable with mij_batch_set_input); valid until the next decode.  The
+ * pixels are complete once the decoder's stream has reached this point */
+void *mij_decoder_device_pixels(mij_decoder *d, int frame, long long *pitch);
+/* HIP-event times of the last reconstruct: {dc + idct, colour}; waits */
+int mij_decoder_reconstruct_ms(mij_decoder *d, float ms[2]);
+/* the decoder's stream, like mij_batch_stream */
+void *mij_decoder_stream(mij_decoder *d);
+/* one call, host to host, mirror of mij_encode: out receives w*h packed
+ * pixels, *w and *h (either may be NULL) the stream's size, as soon as its
+ * headers are read: also with MIJ_ENOSPC, which is returned before any
+ * device work, so a call with cap 0 asks for the size.  MIJ_EINVAL for
+ * a pixels / planes / device_pixels call before reconstruct or after a newer
+ * decode, MIJ_ENOSPC for a short cap (everywhere above) */
+int mij_decode(const uint8_t *jpg, size_t len, int order, uint8_t *out, size_t cap, int *w, int *h);
+
 /* Drop-in entry points of include/brain.h:7-10, on frames of
  * mij_set_input_stride() x mij_set_frame_height() pixels (define.h:3-4,
  * 320x240 by default).  subsample writes the PPM copy to f when f is not

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "mij_host.h"
+#include "mij_pixels.h"
 
 #define HIP_TRY(x)                                                                 \
   do {                                                                             \
@@ -344,6 +345,169 @@ __global__ __launch_bounds__(256) void k_dec_write(SyncArgs a, const long long *
   if (bad) atomicMax(&status[j], 6);
 }
 
+// ---------------------------------------------------------------------------
+// Pixels (DESIGN.md "Decode to pixels"): libjpeg's "islow" IDCT, h2v2 "fancy"
+// upsampling and fixed-point colour conversion, integer only, in two passes
+// through uint8 planes: k_dec_dc + k_dec_dcbase (absolute DCs), k_dec_idct
+// (coefficients -> Y / Cb / Cr samples), k_dec_colour (samples -> packed
+// 3-byte pixels).  The arithmetic itself is mij_pixels.h.
+// The IDCT's sums run in uint32_t: streams no 8-bit image produces wrap
+// instead of overflowing a signed type; encoder-made streams never wrap.
+// ---------------------------------------------------------------------------
+struct RecJob {     // one component of one frame
+  long long off;    // first int16 of its coefficient plane == first byte of its sample plane
+  int nblocks, bw;  // 8x8 blocks, and blocks per row
+  int wg0;          // its first workgroup in k_dec_idct's grid
+  int qt;           // its quantiser: 64 ints (zigzag order) at q + 64 * qt
+  int tile0;        // its first workgroup in k_dec_dc's grid == its first entry of the tile bases
+  int pad;
+};
+
+struct RecFrame {
+  long long planes;  // first byte of the Y plane; Cb at + w*h, Cr at + w*h*5/4
+  long long pix;     // first byte of the pixels, rows 3*w bytes apart
+  int w, h;
+  int wg0;           // its first workgroup in k_dec_colour's grid
+  int pad;
+};
+
+// Absolute DCs in two levels.  A plane's blocks are cut into tiles of
+// DC_TILE; k_dec_dc, one 1024-lane workgroup per tile (so luma and chroma
+// planes load the chip alike), writes every block's DC relative to its tile
+// (each lane DC_PER consecutive blocks, a shuffle scan per wave, the waves'
+// totals through LDS) to dc[off / 64 + block] and the tile's total to
+// tile[blockIdx.x]; k_dec_dcbase, one lane per plane, turns the totals into
+// each tile's base.  k_dec_idct adds the two.  All sums modulo 2^32.
+constexpr int DC_T = 1024, DC_PER = 8, DC_TILE = DC_T * DC_PER;
+
+__device__ __forceinline__ int rec_tile_job(const RecJob *jobs, int njobs, int tile) {
+  int lo = 0, hi = njobs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (jobs[mid].tile0 <= tile) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(DC_T) void k_dec_dc(const RecJob *jobs, int njobs, const int16_t *coefs, int32_t *dc,
+                                                 uint32_t *tile) {
+  __shared__ uint32_t wsum[DC_T / 64];
+  const RecJob job = jobs[rec_tile_job(jobs, njobs, blockIdx.x)];
+  const int16_t *src = coefs + job.off;
+  int32_t *dst = dc + job.off / 64;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b0 = ((int)blockIdx.x - job.tile0) * DC_TILE + (int)threadIdx.x * DC_PER;
+  uint32_t v[DC_PER], s = 0;
+#pragma unroll
+  for (int i = 0; i < DC_PER; i++) {
+    if (b0 + i < job.nblocks) s += (uint32_t)(int32_t)src[64LL * (b0 + i)];
+    v[i] = s;
+  }
+  uint32_t x = s;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  if (lane == 63) wsum[wave] = x;
+  __syncthreads();
+  uint32_t base = x - s, tot = 0;
+#pragma unroll
+  for (int k = 0; k < DC_T / 64; k++) {
+    const uint32_t t = wsum[k];
+    if (k < wave) base += t;
+    tot += t;
+  }
+#pragma unroll
+  for (int i = 0; i < DC_PER; i++)
+    if (b0 + i < job.nblocks) dst[b0 + i] = (int32_t)(base + v[i]);
+  if (threadIdx.x == 0) tile[blockIdx.x] = tot;
+}
+
+// tile totals -> exclusive prefix within each plane (a 3840x2160 luma plane
+// has 16 tiles)
+__global__ __launch_bounds__(64) void k_dec_dcbase(const RecJob *jobs, int njobs, uint32_t *tile) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= njobs) return;
+  const int t0 = jobs[j].tile0, nt = (jobs[j].nblocks + DC_TILE - 1) / DC_TILE;
+  uint32_t run = 0;
+  for (int t = 0; t < nt; t++) {
+    const uint32_t v = tile[t0 + t];
+    tile[t0 + t] = run;
+    run += v;
+  }
+}
+
+__device__ __forceinline__ int rec_job_of(const RecJob *jobs, int njobs, int wg) {
+  int lo = 0, hi = njobs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (jobs[mid].wg0 <= wg) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// One lane per 8x8 block, 256 blocks of one component per workgroup.  The
+// workgroup's 32 KiB of coefficients come in with coalesced 16-byte loads
+// and are staged in LDS, a block's 8 int4 in a slot of 9 (a lane's 16-byte
+// reads then fall on distinct bank groups); the lane dequantises into
+// natural order (all indices compile-time: registers), runs the column pass
+// (descale 11) and the row pass (descale 18), and stores 8 bytes per row.
+__global__ __launch_bounds__(256) void k_dec_idct(const RecJob *jobs, int njobs, const int16_t *coefs,
+                                                  const int32_t *dc, const uint32_t *tile, const int32_t *q,
+                                                  uint8_t *planes) {
+  __shared__ int4 stage[256 * 9];
+  const RecJob job = jobs[rec_job_of(jobs, njobs, blockIdx.x)];
+  const int first = ((int)blockIdx.x - job.wg0) * 256;
+  const int nb = min(256, job.nblocks - first);
+  const int4 *src = (const int4 *)(coefs + job.off + 64LL * first);
+  for (int i = threadIdx.x; i < nb * 8; i += 256) stage[(i >> 3) * 9 + (i & 7)] = src[i];
+  __syncthreads();
+  if ((int)threadIdx.x >= nb) return;
+  const int blk = first + threadIdx.x;
+  union {
+    int4 v[8];
+    int16_t c[64];
+  } in;
+#pragma unroll
+  for (int k = 0; k < 8; k++) in.v[k] = stage[threadIdx.x * 9 + k];
+  uint32_t rows[8][2];
+  const uint32_t dc_abs = (uint32_t)dc[job.off / 64 + blk] + tile[job.tile0 + blk / DC_TILE];
+  idct_block(in.c, dc_abs, q + 64 * job.qt, rows);
+  const int by = blk / job.bw, bx = blk - by * job.bw;
+  const long long pitch = 8LL * job.bw;
+  uint8_t *dst = planes + job.off + 8LL * by * pitch + 8 * bx;
+#pragma unroll
+  for (int r = 0; r < 8; r++)  // 8-byte aligned: off % 64 == 0, pitch % 8 == 0
+    store_as(dst + r * pitch, W2{rows[r][0], rows[r][1]});
+}
+
+__device__ __forceinline__ int rec_frame_of(const RecFrame *fr, int n, int wg) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (fr[mid].wg0 <= wg) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// One lane per 16 x 2 output pixels (colour_tile, mij_pixels.h), a frame's
+// tiles in raster order, 256 per workgroup; no workgroup spans two frames.
+__global__ __launch_bounds__(256) void k_dec_colour(const RecFrame *frames, int nframes, const uint8_t *planes,
+                                                    uint8_t *pix, int rgb) {
+  const RecFrame fr = frames[rec_frame_of(frames, nframes, blockIdx.x)];
+  const int groups = fr.w >> 4;
+  const int idx = ((int)blockIdx.x - fr.wg0) * 256 + (int)threadIdx.x;
+  if (idx >= (fr.h >> 1) * groups) return;
+  const int r = idx / groups, g = idx - r * groups;
+  const uint8_t *Y = planes + fr.planes;
+  const uint8_t *Cb = Y + (long long)fr.w * fr.h, *Cr = Cb + ((long long)fr.w * fr.h >> 2);
+  colour_tile(Y, Cb, Cr, fr.w, fr.h, r, g, rgb, pix + fr.pix);
+}
+
 }  // namespace mij
 
 // ---------------------------------------------------------------------------
@@ -500,6 +664,18 @@ struct mij_decoder {
   std::vector<Parsed> parsed;
   long long plane_px = 0;  // max_w * max_h: Y plane; Cb/Cr a quarter each
   int n = 0;
+  // pixels (mij_decoder_reconstruct): allocated on its first call
+  bool rec_ready = false;  // buffers and events exist
+  bool rec_valid = false;  // they hold the last decode's frames
+  uint8_t *d_planes = nullptr, *d_pix = nullptr;
+  int32_t *d_dc = nullptr, *d_recq = nullptr;
+  uint32_t *d_tile = nullptr;
+  mij::RecJob *d_rjobs = nullptr;
+  mij::RecFrame *d_rframes = nullptr;
+  std::vector<mij::RecJob> h_rjobs;  // kept: the uploads are asynchronous
+  std::vector<mij::RecFrame> h_rframes;
+  std::vector<int32_t> h_recq;
+  hipEvent_t rec_ev[3] = {nullptr, nullptr, nullptr};
 };
 
 static void decoder_free(mij_decoder *d) {
@@ -517,6 +693,15 @@ static void decoder_free(mij_decoder *d) {
   hipFree(d->d_exit[1]);
   hipFree(d->d_nblk);
   hipFree(d->d_base);
+  hipFree(d->d_planes);
+  hipFree(d->d_pix);
+  hipFree(d->d_dc);
+  hipFree(d->d_recq);
+  hipFree(d->d_tile);
+  hipFree(d->d_rjobs);
+  hipFree(d->d_rframes);
+  for (hipEvent_t e : d->rec_ev)
+    if (e) hipEventDestroy(e);
   if (d->h_blob) hipHostFree(d->h_blob);
   if (d->stream) hipStreamDestroy(d->stream);
   delete d;
@@ -616,6 +801,7 @@ extern "C" int mij_decoder_decode(mij_decoder *d, const uint8_t *const *jpgs, co
   if (!d || !jpgs || !lens || n < 1 || n > d->cap) return mij_fail(MIJ_EINVAL, "decoder_decode: bad args");
   HIP_TRY(hipSetDevice(d->dev));
   d->n = 0;  // set to n only once every stream decoded cleanly
+  d->rec_valid = false;  // pixels of an earlier decode are no longer served
   d->parsed.assign(n, Parsed());
   // host work per stream in parallel: parse (finds the scan ends), then
   // unstuff each scan into its slot (sized by the raw length, an upper bound)
@@ -755,4 +941,188 @@ extern "C" int mij_decoder_coefs(mij_decoder *d, int frame, int16_t *Y, int16_t 
 extern "C" void *mij_decoder_device_coefs(mij_decoder *d, int frame) {
   if (!d || frame < 0 || frame >= d->n) return nullptr;
   return d->d_coef + frame * (d->plane_px * 3 / 2);
+}
+
+// ---------------------------------------------------------------------------
+// pixels: host side
+// ---------------------------------------------------------------------------
+static int decoder_rec_buffers(mij_decoder *d) {
+  if (d->rec_ready) return MIJ_OK;
+  const size_t fs = (size_t)d->plane_px * 3 / 2, cap = (size_t)d->cap;
+  auto alloc = [&]() -> int {
+    HIP_TRY(hipMalloc((void **)&d->d_planes, cap * fs));
+    HIP_TRY(hipMalloc((void **)&d->d_pix, cap * (size_t)d->plane_px * 3));
+    HIP_TRY(hipMalloc((void **)&d->d_dc, cap * (fs / 64) * sizeof(int32_t)));
+    HIP_TRY(hipMalloc((void **)&d->d_recq, cap * 128 * sizeof(int32_t)));
+    // tiles: a plane of b blocks has at most b / DC_TILE + 1
+    HIP_TRY(hipMalloc((void **)&d->d_tile, cap * (fs / 64 / mij::DC_TILE + 3) * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void **)&d->d_rjobs, cap * 3 * sizeof(mij::RecJob)));
+    HIP_TRY(hipMalloc((void **)&d->d_rframes, cap * sizeof(mij::RecFrame)));
+    for (hipEvent_t &e : d->rec_ev) HIP_TRY(hipEventCreate(&e));
+    return MIJ_OK;
+  };
+  if (int rc = alloc()) {  // all or nothing: the next call starts over
+    for (void **p : {(void **)&d->d_planes, (void **)&d->d_pix, (void **)&d->d_dc, (void **)&d->d_recq,
+                     (void **)&d->d_tile, (void **)&d->d_rjobs, (void **)&d->d_rframes}) {
+      hipFree(*p);
+      *p = nullptr;
+    }
+    for (hipEvent_t &e : d->rec_ev) {
+      if (e) hipEventDestroy(e);
+      e = nullptr;
+    }
+    return rc;
+  }
+  d->rec_ready = true;
+  return MIJ_OK;
+}
+
+extern "C" int mij_decoder_reconstruct(mij_decoder *d, int order) {
+  mij_clear_error();
+  if (!d) return mij_fail(MIJ_EINVAL, "decoder_reconstruct: no decoder");
+  if (order != MIJ_PIX_BGR && order != MIJ_PIX_RGB)
+    return mij_fail(MIJ_EINVAL, "decoder_reconstruct: pixel order %d", order);
+  if (d->n < 1) return mij_fail(MIJ_EINVAL, "decoder_reconstruct: no decoded frames");
+  HIP_TRY(hipSetDevice(d->dev));
+  if (int rc = decoder_rec_buffers(d)) return rc;
+  // the previous call's uploads read these vectors: let them finish first
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  d->rec_valid = false;
+  const int n = d->n;
+  const long long fs = d->plane_px * 3 / 2;
+  d->h_rjobs.resize(3 * (size_t)n);
+  d->h_rframes.resize(n);
+  d->h_recq.resize(128 * (size_t)n);
+  long long idct_wgs = 0, col_wgs = 0, tiles = 0;
+  for (int f = 0; f < n; f++) {
+    const Parsed &P = d->parsed[f];
+    if (!P.have_dqt[0] || !P.have_dqt[1]) return mij_fail(MIJ_EJPEG, "stream %d: DQT missing", f);
+    for (int t = 0; t < 2; t++)
+      for (int z = 0; z < 64; z++) d->h_recq[128 * f + 64 * t + z] = P.dqt[t][z];
+    const long long ny = (long long)P.w * P.h;
+    const long long off[3] = {f * fs, f * fs + ny, f * fs + ny + ny / 4};
+    for (int c = 0; c < 3; c++) {
+      mij::RecJob &j = d->h_rjobs[3 * f + c];
+      j.off = off[c];
+      j.nblocks = (int)(c ? ny / 256 : ny / 64);
+      j.bw = c ? P.w / 16 : P.w / 8;
+      j.wg0 = (int)idct_wgs;
+      j.qt = 2 * f + (c != 0);
+      j.tile0 = (int)tiles;
+      j.pad = 0;
+      idct_wgs += (j.nblocks + 255) / 256;
+      tiles += (j.nblocks + mij::DC_TILE - 1) / mij::DC_TILE;
+    }
+    mij::RecFrame &fr = d->h_rframes[f];
+    fr.planes = f * fs;
+    fr.pix = f * d->plane_px * 3;
+    fr.w = P.w;
+    fr.h = P.h;
+    fr.wg0 = (int)col_wgs;
+    fr.pad = 0;
+    col_wgs += ((long long)(P.h / 2) * (P.w / 16) + 255) / 256;
+  }
+  if (idct_wgs > 0x7fffffff || col_wgs > 0x7fffffff) return mij_fail(MIJ_EINVAL, "decoder_reconstruct: too many blocks");
+  HIP_TRY(hipMemcpyAsync(d->d_rjobs, d->h_rjobs.data(), d->h_rjobs.size() * sizeof(mij::RecJob),
+                         hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->d_rframes, d->h_rframes.data(), d->h_rframes.size() * sizeof(mij::RecFrame),
+                         hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->d_recq, d->h_recq.data(), d->h_recq.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                         d->stream));
+  HIP_TRY(hipEventRecord(d->rec_ev[0], d->stream));
+  hipLaunchKernelGGL(mij::k_dec_dc, dim3((unsigned)tiles), dim3(mij::DC_T), 0, d->stream, d->d_rjobs, 3 * n,
+                     d->d_coef, d->d_dc, d->d_tile);
+  hipLaunchKernelGGL(mij::k_dec_dcbase, dim3((3 * n + 63) / 64), dim3(64), 0, d->stream, d->d_rjobs, 3 * n,
+                     d->d_tile);
+  hipLaunchKernelGGL(mij::k_dec_idct, dim3((unsigned)idct_wgs), dim3(256), 0, d->stream, d->d_rjobs, 3 * n,
+                     d->d_coef, d->d_dc, d->d_tile, d->d_recq, d->d_planes);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(d->rec_ev[1], d->stream));
+  hipLaunchKernelGGL(mij::k_dec_colour, dim3((unsigned)col_wgs), dim3(256), 0, d->stream, d->d_rframes, n,
+                     d->d_planes, d->d_pix, order == MIJ_PIX_RGB);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(d->rec_ev[2], d->stream));
+  d->rec_valid = true;
+  return MIJ_OK;
+}
+
+// the frame's geometry once pixels of the last decode exist
+static int rec_frame(mij_decoder *d, int frame, const char *what, const Parsed **P) {
+  if (!d) return mij_fail(MIJ_EINVAL, "%s: no decoder", what);
+  if (!d->rec_valid) return mij_fail(MIJ_EINVAL, "%s: no mij_decoder_reconstruct since the last decode", what);
+  if (frame < 0 || frame >= d->n) return mij_fail(MIJ_EINVAL, "%s: frame %d of %d", what, frame, d->n);
+  *P = &d->parsed[frame];
+  return MIJ_OK;
+}
+
+extern "C" int mij_decoder_pixels(mij_decoder *d, int frame, uint8_t *dst, size_t cap, long long pitch) {
+  mij_clear_error();
+  const Parsed *P;
+  if (int rc = rec_frame(d, frame, "decoder_pixels", &P)) return rc;
+  if (!dst) return mij_fail(MIJ_EINVAL, "decoder_pixels: dst is NULL");
+  const long long row = 3LL * P->w;
+  if (pitch == 0) pitch = row;
+  if (pitch < row) return mij_fail(MIJ_EINVAL, "decoder_pixels: pitch %lld < %lld", pitch, row);
+  const unsigned long long need = (unsigned long long)(P->h - 1) * pitch + row;
+  if (cap < need) return mij_fail(MIJ_ENOSPC, "decoder_pixels: need %llu bytes", need);
+  HIP_TRY(hipSetDevice(d->dev));
+  HIP_TRY(hipMemcpy2DAsync(dst, (size_t)pitch, d->d_pix + frame * d->plane_px * 3, (size_t)row, (size_t)row, P->h,
+                           hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  return MIJ_OK;
+}
+
+extern "C" int mij_decoder_planes(mij_decoder *d, int frame, uint8_t *Y, uint8_t *Cb, uint8_t *Cr) {
+  mij_clear_error();
+  const Parsed *P;
+  if (int rc = rec_frame(d, frame, "decoder_planes", &P)) return rc;
+  if (!Y || !Cb || !Cr) return mij_fail(MIJ_EINVAL, "decoder_planes: NULL plane");
+  HIP_TRY(hipSetDevice(d->dev));
+  const long long ny = (long long)P->w * P->h;
+  const uint8_t *src = d->d_planes + frame * (d->plane_px * 3 / 2);
+  HIP_TRY(hipMemcpyAsync(Y, src, ny, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipMemcpyAsync(Cb, src + ny, ny / 4, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipMemcpyAsync(Cr, src + ny + ny / 4, ny / 4, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  return MIJ_OK;
+}
+
+extern "C" void *mij_decoder_device_pixels(mij_decoder *d, int frame, long long *pitch) {
+  mij_clear_error();
+  const Parsed *P;
+  if (rec_frame(d, frame, "decoder_device_pixels", &P)) return nullptr;
+  if (pitch) *pitch = 3LL * P->w;
+  return d->d_pix + frame * d->plane_px * 3;
+}
+
+extern "C" int mij_decoder_reconstruct_ms(mij_decoder *d, float ms[2]) {
+  mij_clear_error();
+  if (!d || !ms) return mij_fail(MIJ_EINVAL, "decoder_reconstruct_ms: bad args");
+  if (!d->rec_valid) return mij_fail(MIJ_EINVAL, "decoder_reconstruct_ms: no mij_decoder_reconstruct since the last decode");
+  HIP_TRY(hipSetDevice(d->dev));
+  HIP_TRY(hipEventSynchronize(d->rec_ev[2]));
+  HIP_TRY(hipEventElapsedTime(&ms[0], d->rec_ev[0], d->rec_ev[1]));
+  HIP_TRY(hipEventElapsedTime(&ms[1], d->rec_ev[1], d->rec_ev[2]));
+  return MIJ_OK;
+}
+
+extern "C" void *mij_decoder_stream(mij_decoder *d) { return d ? (void *)d->stream : nullptr; }
+
+extern "C" int mij_decode(const uint8_t *jpg, size_t len, int order, uint8_t *out, size_t cap, int *w, int *h) {
+  mij_clear_error();
+  if (!jpg || !out) return mij_fail(MIJ_EINVAL, "mij_decode: NULL buffer");
+  if (order != MIJ_PIX_BGR && order != MIJ_PIX_RGB) return mij_fail(MIJ_EINVAL, "mij_decode: pixel order %d", order);
+  Parsed P;  // the size first: the decoder is made for it
+  if (int rc = parse(jpg, len, P, 0)) return rc;
+  if (w) *w = P.w;
+  if (h) *h = P.h;
+  const unsigned long long need = 3ULL * P.w * P.h;
+  if (cap < need) return mij_fail(MIJ_ENOSPC, "mij_decode: need %llu bytes", need);
+  mij_decoder *d = mij_decoder_create(mij_drop_device(), P.w, P.h, 1);
+  if (!d) return mij_last_error();
+  int rc = mij_decoder_decode(d, &jpg, &len, 1);
+  if (!rc) rc = mij_decoder_reconstruct(d, order);
+  if (!rc) rc = mij_decoder_pixels(d, 0, out, cap, 0);
+  decoder_free(d);  // (leaves the failure's message in place)
+  return rc;
 }

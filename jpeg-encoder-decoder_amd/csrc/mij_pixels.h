@@ -1,0 +1,195 @@
+// mij_pixels.h -- the decoder's pixel arithmetic (DESIGN.md "Decode to
+// pixels"): libjpeg's "islow" IDCT, h2v2 "fancy" upsampling and fixed-point
+// colour conversion, integer only.  Shared by the kernels of mij_decode.hip
+// and the host check tests/pixels_check.cpp, so the CPU suite runs the very
+// code the GPU runs.  The IDCT's products and sums are taken modulo 2^32
+// (uint32_t): a stream no 8-bit image produces wraps instead of overflowing
+// a signed type; encoder-made streams never come near the limit.
+#pragma once
+#include <stdint.h>
+
+#ifdef __HIPCC__
+#define MIJ_HD __host__ __device__ __forceinline__
+#define MIJ_UNROLL _Pragma("unroll")
+#else
+#define MIJ_HD inline
+#define MIJ_UNROLL
+#endif
+
+namespace mij {
+
+// natural position of zigzag index z
+#define MIJ_ZIGZAG                                                                                    \
+  {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,            \
+   41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,            \
+   30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63}
+
+MIJ_HD uint32_t clamp255(int32_t v) { return (uint32_t)(v < 0 ? 0 : v > 255 ? 255 : v); }
+
+// the 1-D pass of the "islow" IDCT (CONST_BITS 13), outputs descaled by SH
+template <int SH>
+MIJ_HD void idct8(uint32_t i0, uint32_t i1, uint32_t i2, uint32_t i3, uint32_t i4, uint32_t i5, uint32_t i6,
+                  uint32_t i7, int32_t o[8]) {
+  uint32_t z1 = (i2 + i6) * 4433u;
+  const uint32_t t2 = z1 - i6 * 15137u, t3 = z1 + i2 * 6270u;
+  const uint32_t t0 = (i0 + i4) << 13, t1 = (i0 - i4) << 13;
+  const uint32_t t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  uint32_t o0 = i7, o1 = i5, o2 = i3, o3 = i1;
+  z1 = o0 + o3;
+  uint32_t z2 = o1 + o2, z3 = o0 + o2, z4 = o1 + o3;
+  const uint32_t z5 = (z3 + z4) * 9633u;
+  o0 *= 2446u;
+  o1 *= 16819u;
+  o2 *= 25172u;
+  o3 *= 12299u;
+  z1 *= (uint32_t)-7373;
+  z2 *= (uint32_t)-20995;
+  z3 = z3 * (uint32_t)-16069 + z5;
+  z4 = z4 * (uint32_t)-3196 + z5;
+  o0 += z1 + z3;
+  o1 += z2 + z4;
+  o2 += z2 + z3;
+  o3 += z1 + z4;
+  constexpr uint32_t R = 1u << (SH - 1);
+  o[0] = (int32_t)(t10 + o3 + R) >> SH;
+  o[1] = (int32_t)(t11 + o2 + R) >> SH;
+  o[2] = (int32_t)(t12 + o1 + R) >> SH;
+  o[3] = (int32_t)(t13 + o0 + R) >> SH;
+  o[4] = (int32_t)(t13 - o0 + R) >> SH;
+  o[5] = (int32_t)(t12 - o1 + R) >> SH;
+  o[6] = (int32_t)(t11 - o2 + R) >> SH;
+  o[7] = (int32_t)(t10 - o3 + R) >> SH;
+}
+
+// One 8x8 block: c = its 64 zigzag-ordered quantised coefficients (c[0] is
+// ignored: dc is the absolute DC), qz = the quantiser in zigzag order.
+// rows[r] = the 8 samples of row r, little-endian in two words.  Every index
+// is a compile-time constant once unrolled, so on the GPU all arrays are
+// registers.
+MIJ_HD void idct_block(const int16_t *c, uint32_t dc, const int32_t *qz, uint32_t rows[8][2]) {
+  constexpr uint8_t zz[64] = MIJ_ZIGZAG;
+  uint32_t d[64];
+  d[0] = dc * (uint32_t)qz[0];
+  MIJ_UNROLL
+  for (int z = 1; z < 64; z++) d[zz[z]] = (uint32_t)(int32_t)c[z] * (uint32_t)qz[z];
+  int32_t ws[64];
+  MIJ_UNROLL
+  for (int col = 0; col < 8; col++) {  // down each column, descale 11
+    int32_t o[8];
+    idct8<11>(d[col], d[8 + col], d[16 + col], d[24 + col], d[32 + col], d[40 + col], d[48 + col], d[56 + col], o);
+  MIJ_UNROLL
+    for (int k = 0; k < 8; k++) ws[8 * k + col] = o[k];
+  }
+  MIJ_UNROLL
+  for (int r = 0; r < 8; r++) {  // along each row, descale 18, level shift, clamp
+    int32_t o[8];
+    idct8<18>(ws[8 * r], ws[8 * r + 1], ws[8 * r + 2], ws[8 * r + 3], ws[8 * r + 4], ws[8 * r + 5], ws[8 * r + 6],
+              ws[8 * r + 7], o);
+    rows[r][0] = clamp255(o[0] + 128) | clamp255(o[1] + 128) << 8 | clamp255(o[2] + 128) << 16 |
+                 clamp255(o[3] + 128) << 24;
+    rows[r][1] = clamp255(o[4] + 128) | clamp255(o[5] + 128) << 8 | clamp255(o[6] + 128) << 16 |
+                 clamp255(o[7] + 128) << 24;
+  }
+}
+
+// 16 upsampled chroma samples (0..255) of one output row.  p = chroma
+// samples c0-1 .. c0+8 of the chroma row itself, nb = the same columns of its
+// upper (for the upper output row) or lower neighbour; the caller replicates
+// the plane's edge rows and columns (jdsample.c h2v2_fancy_upsample)
+MIJ_HD void upsample16(const int p[10], const int nb[10], int out[16]) {
+  int s[10];
+  MIJ_UNROLL
+  for (int k = 0; k < 10; k++) s[k] = 3 * p[k] + nb[k];
+  MIJ_UNROLL
+  for (int k = 0; k < 8; k++) {
+    out[2 * k] = (3 * s[k + 1] + s[k] + 8) >> 4;
+    out[2 * k + 1] = (3 * s[k + 1] + s[k + 2] + 7) >> 4;
+  }
+}
+
+// 16 pixels -> 48 packed bytes in 12 little-endian words; y = 16 luma bytes in
+// 4 words, cb / cr = upsample16's output; rgb: R,G,B order, else B,G,R.
+// jdcolor.c's R = Y + ((91881 * (Cr - 128) + 32768) >> 16) and so on, the
+// - 128 folded into the rounding constant (sums of integers: the same value)
+MIJ_HD void colour16(const uint32_t y[4], const int cb[16], const int cr[16], int rgb, uint32_t wd[12]) {
+  MIJ_UNROLL
+  for (int k = 0; k < 12; k++) wd[k] = 0;
+  MIJ_UNROLL
+  for (int p = 0; p < 16; p++) {
+    const int yy = (int)((y[p >> 2] >> (8 * (p & 3))) & 255);
+    const uint32_t R = clamp255(yy + ((91881 * cr[p] + (32768 - 128 * 91881)) >> 16));
+    const uint32_t G = clamp255(yy + ((-22554 * cb[p] - 46802 * cr[p] + (32768 + 128 * (22554 + 46802))) >> 16));
+    const uint32_t B = clamp255(yy + ((116130 * cb[p] + (32768 - 128 * 116130)) >> 16));
+    const uint32_t ch[3] = {rgb ? R : B, G, rgb ? B : R};
+  MIJ_UNROLL
+    for (int k = 0; k < 3; k++) wd[(3 * p + k) >> 2] |= ch[k] << (8 * ((3 * p + k) & 3));
+  }
+}
+
+// aligned 8- and 16-byte moves (one load or store instruction each on the GPU)
+struct alignas(8) W2 {
+  uint32_t x, y;
+};
+struct alignas(16) W4 {
+  uint32_t x, y, z, w;
+};
+template <class T>
+MIJ_HD T load_as(const uint8_t *p) {
+  T v;
+  __builtin_memcpy(&v, __builtin_assume_aligned(p, alignof(T)), sizeof(T));
+  return v;
+}
+template <class T>
+MIJ_HD void store_as(uint8_t *p, const T &v) {
+  __builtin_memcpy(__builtin_assume_aligned(p, alignof(T)), &v, sizeof(T));
+}
+
+// chroma samples c0-1 .. c0+8 of a row (c0 % 8 == 0; cl / cr: the two halo
+// columns, already clamped to the plane)
+MIJ_HD void chroma10(const uint8_t *row, int c0, int cl, int cr, int v[10]) {
+  const W2 m = load_as<W2>(row + c0);
+  v[0] = row[cl];
+  MIJ_UNROLL
+  for (int k = 0; k < 4; k++) {
+    v[1 + k] = (int)((m.x >> (8 * k)) & 255);
+    v[5 + k] = (int)((m.y >> (8 * k)) & 255);
+  }
+  v[9] = row[cr];
+}
+
+// Output rows 2r and 2r+1, columns 16g .. 16g+15 of a w x h frame: chroma
+// row r with rows r-1 / r+1 and columns 8g-1 / 8g+8 clamped to the plane, so
+// nothing outside the frame's three planes is read.  Y: w*h samples, Cb and
+// Cr: (w/2)*(h/2); pix: rows 3*w bytes apart.  Each output row leaves as
+// three aligned 16-byte stores (3*w and 48*g are multiples of 16).
+MIJ_HD void colour_tile(const uint8_t *Y, const uint8_t *Cb, const uint8_t *Cr, int w, int h, int r, int g, int rgb,
+                        uint8_t *pix) {
+  const int cw = w >> 1, ch = h >> 1;
+  const int ru = r > 0 ? r - 1 : 0, rd = r + 1 < ch ? r + 1 : ch - 1;
+  const int c0 = 8 * g, cl = c0 > 0 ? c0 - 1 : 0, cr = c0 + 8 < cw ? c0 + 8 : cw - 1;
+  int mid[10], nb[10], cb[2][16], crv[2][16];
+  chroma10(Cb + (long long)r * cw, c0, cl, cr, mid);
+  chroma10(Cb + (long long)ru * cw, c0, cl, cr, nb);
+  upsample16(mid, nb, cb[0]);
+  chroma10(Cb + (long long)rd * cw, c0, cl, cr, nb);
+  upsample16(mid, nb, cb[1]);
+  chroma10(Cr + (long long)r * cw, c0, cl, cr, mid);
+  chroma10(Cr + (long long)ru * cw, c0, cl, cr, nb);
+  upsample16(mid, nb, crv[0]);
+  chroma10(Cr + (long long)rd * cw, c0, cl, cr, nb);
+  upsample16(mid, nb, crv[1]);
+  MIJ_UNROLL
+  for (int row = 0; row < 2; row++) {
+    const long long y = 2LL * r + row;
+    const W4 yv = load_as<W4>(Y + y * w + 16 * g);
+    const uint32_t yw[4] = {yv.x, yv.y, yv.z, yv.w};
+    uint32_t wd[12];
+    colour16(yw, cb[row], crv[row], rgb, wd);
+    uint8_t *dst = pix + y * 3 * w + 48 * g;
+    store_as(dst, W4{wd[0], wd[1], wd[2], wd[3]});
+    store_as(dst + 16, W4{wd[4], wd[5], wd[6], wd[7]});
+    store_as(dst + 32, W4{wd[8], wd[9], wd[10], wd[11]});
+  }
+}
+
+}  // namespace mij

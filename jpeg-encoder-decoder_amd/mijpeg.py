@@ -36,6 +36,8 @@ EXPORTS = [
     "subsample", "store", "compare", "enlargeAdjust", "mij_set_frame_height",
     "mij_decoder_create", "mij_decoder_destroy", "mij_decoder_decode", "mij_decoder_info",
     "mij_decoder_coefs", "mij_decoder_device_coefs", "mij_decoder_passes",
+    "mij_decoder_reconstruct", "mij_decoder_pixels", "mij_decoder_planes", "mij_decoder_device_pixels",
+    "mij_decoder_reconstruct_ms", "mij_decoder_stream", "mij_decode",
     "mij_detector_create", "mij_detector_destroy", "mij_detector_subsample", "mij_detector_compare",
     "mij_detector_step", "mij_detector_launch", "mij_detector_store", "mij_detector_upload", "mij_detector_get_plane",
     "mij_detector_set_plane", "mij_detector_mask", "mij_detector_stream",
@@ -203,6 +205,15 @@ def load() -> C.CDLL:
         lib.mij_decoder_device_coefs.restype = p
         lib.mij_decoder_device_coefs.argtypes = [p, i]
         lib.mij_decoder_passes.argtypes = [p]
+        lib.mij_decoder_reconstruct.argtypes = [p, i]
+        lib.mij_decoder_pixels.argtypes = [p, i, p, sz, C.c_longlong]
+        lib.mij_decoder_planes.argtypes = [p, i, p, p, p]
+        lib.mij_decoder_device_pixels.restype = p
+        lib.mij_decoder_device_pixels.argtypes = [p, i, C.POINTER(C.c_longlong)]
+        lib.mij_decoder_reconstruct_ms.argtypes = [p, p]
+        lib.mij_decoder_stream.restype = p
+        lib.mij_decoder_stream.argtypes = [p]
+        lib.mij_decode.argtypes = [p, sz, i, p, sz, C.POINTER(i), C.POINTER(i)]
         lib.subsample.restype = None
         lib.subsample.argtypes = [p, p, p]
         lib.store.restype = None
@@ -859,9 +870,34 @@ def drop_in_enlarge_adjust(area, W: int, H: int):
 
 # ---- round-trip verifier ---------------------------
 
+PIXEL_ORDERS = {"bgr": 0, "rgb": 1}  # MIJ_PIX_*
+
+
+def _order(order: str) -> int:
+    if order not in PIXEL_ORDERS:
+        raise MijError(f"pixel order {order!r}: 'bgr' or 'rgb'")
+    return PIXEL_ORDERS[order]
+
+
+def decode(jpg: bytes, order: str = "bgr") -> np.ndarray:
+    """mij_decode: one baseline JFIF stream -> (h, w, 3) uint8 pixels, host to host."""
+    lib = load()
+    buf = np.frombuffer(jpg, np.uint8)
+    w, h = C.c_int(0), C.c_int(0)
+    probe = np.zeros(1, np.uint8)
+    rc = lib.mij_decode(_ptr(buf), buf.size, _order(order), _ptr(probe), 0, C.byref(w), C.byref(h))
+    if rc != 4:  # MIJ_ENOSPC once the size is known, before any device work
+        _check(rc, "mij_decode")
+    out = np.zeros((h.value, w.value, 3), np.uint8)
+    _check(lib.mij_decode(_ptr(buf), buf.size, _order(order), _ptr(out), out.nbytes, C.byref(w), C.byref(h)),
+           "mij_decode")
+    return out
+
+
 class Decoder:
     """Baseline JFIF streams (the shape encoder.c:549-644 writes) -> the
-    encoder's coefficient planes, entropy-decoded on the GPU."""
+    encoder's coefficient planes, entropy-decoded on the GPU, and from those
+    (reconstruct) the pixels libjpeg would give."""
 
     def __init__(self, max_w: int, max_h: int, max_frames: int, device: int = 0):
         self.lib = load()
@@ -904,3 +940,48 @@ class Decoder:
         Cr = np.zeros(w * h // 4, np.int16)
         _check(self.lib.mij_decoder_coefs(self.h_, frame, _ptr(Y), _ptr(Cb), _ptr(Cr)), "decoder_coefs")
         return Y, Cb, Cr
+
+    def reconstruct(self, order: str = "bgr") -> None:
+        """every frame of the last decode -> planes and pixels (asynchronous)"""
+        _check(self.lib.mij_decoder_reconstruct(self.h_, _order(order)), "decoder_reconstruct")
+
+    def pixels(self, frame: int, pitch: int = 0, out: np.ndarray | None = None) -> np.ndarray:
+        """(h, w, 3) uint8 pixels of `frame`; with `pitch` (bytes, >= 3*w) the
+        rows land pitch bytes apart in `out` (a flat uint8 array, or a new
+        one), whose other bytes are left as they are"""
+        w, h, _ = self.info(frame)
+        if not pitch:
+            out = np.zeros((h, w, 3), np.uint8)
+        elif out is None:
+            out = np.zeros(h * pitch, np.uint8)
+        _check(self.lib.mij_decoder_pixels(self.h_, frame, _ptr(out), out.nbytes, pitch), "decoder_pixels")
+        return out
+
+    def planes(self, frame: int):
+        """the IDCT output before upsampling: Y (h, w), Cb and Cr (h/2, w/2)"""
+        w, h, _ = self.info(frame)
+        Y = np.zeros((h, w), np.uint8)
+        Cb = np.zeros((h // 2, w // 2), np.uint8)
+        Cr = np.zeros((h // 2, w // 2), np.uint8)
+        _check(self.lib.mij_decoder_planes(self.h_, frame, _ptr(Y), _ptr(Cb), _ptr(Cr)), "decoder_planes")
+        return Y, Cb, Cr
+
+    def device_pixels(self, frame: int):
+        """(device address, pitch in bytes) of `frame`'s pixels: valid until
+        the next decode, complete once the decoder's stream (stream_ptr) has
+        run the reconstruct"""
+        pitch = C.c_longlong(0)
+        ptr = self.lib.mij_decoder_device_pixels(self.h_, frame, C.byref(pitch))
+        if not ptr:
+            _check(self.lib.mij_last_error() or 1, "decoder_device_pixels")
+        return int(ptr), int(pitch.value)
+
+    def reconstruct_ms(self):
+        """(dc + idct, colour) HIP-event milliseconds of the last reconstruct; waits for it"""
+        ms = (C.c_float * 2)()
+        _check(self.lib.mij_decoder_reconstruct_ms(self.h_, ms), "decoder_reconstruct_ms")
+        return float(ms[0]), float(ms[1])
+
+    def stream_ptr(self) -> int:
+        """the decoder's hipStream_t (Batch.set_stream orders an encode behind a reconstruct)"""
+        return int(self.lib.mij_decoder_stream(self.h_) or 0)
