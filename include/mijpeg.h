@@ -84,7 +84,9 @@ enum {
                            defined behaviour (code length >= 32 etc.) */
     MIJ_EPPM = 6,       /* PPM rejected by the rules of utils/original.c:294-365 */
     MIJ_EIO = 7,        /* file could not be opened, read or written */
-    MIJ_EJPEG = 8,      /* decoder: stream outside the supported JFIF subset or corrupt */
+    MIJ_EJPEG = 8,      /* decoder: not a baseline stream of the accepted subset (8-bit SOF0, greyscale
+                         * or YCbCr 4:4:4 / 4:2:2 / 4:2:0, one interleaved scan or the encoder's three
+                         * scans), or corrupt; the message names the stream and the reason */
     MIJ_EHANG = 9       /* a device-side wait (pack look-back, ticket) outlasted its
                            bound: the frame's device state was corrupted; the
                            frame fails instead of the launch hanging */
@@ -490,6 +492,29 @@ int mij_decoder_passes(mij_decoder *d);
 /* device address of stream `frame`'s planes (Y, then Cb, then Cr) */
 void *mij_decoder_device_coefs(mij_decoder *d, int frame);
 
+/* ---- ordinary baseline files -------------------------------------------------
+ * mij_decoder_decode also accepts what libjpeg, Pillow, cameras and browsers
+ * write: 8-bit baseline (SOF0, Huffman), greyscale or YCbCr with luma 1x1
+ * (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0) and chroma 1x1, any width and height
+ * up to the decoder's, one interleaved scan, DQT ids 0..3, arbitrary
+ * component ids, restart intervals.  Such a frame's planes are padded to
+ * whole MCUs; mij_decoder_coefs / _planes are defined as the encoder's layout
+ * and return MIJ_EINVAL on it: use the three calls below, which work on
+ * every frame.  The memory for such frames is allocated when a decode call
+ * first holds one and grows (is freed and allocated again) when a call needs
+ * more; a decoder that only sees the encoder's streams allocates none.
+ *
+ * layout: out[0..8] = w, h, components, max H, max V, MCUs across, MCUs
+ * down, restart interval (0 = none), 1 if one interleaved scan; then per
+ * component H, V, Tq, blocks across, blocks down of its padded plane.
+ * MIJ_ENOSPC if n < 9 + 5 * components (at most 24). */
+#define MIJ_LAYOUT_MAX 24
+int mij_decoder_layout(mij_decoder *d, int frame, int *out, int n);
+/* host copy of component comp's padded plane: blocks in raster order, 64
+ * zigzag-ordered quantized coefficients each, the DC ABSOLUTE (the view
+ * libjpeg's jpeg_read_coefficients gives); cap in coefficients */
+int mij_decoder_component(mij_decoder *d, int frame, int comp, int16_t *dst, size_t cap);
+
 /* ---- decode to pixels -------------------------------------------------------
  * The decoded coefficients through libjpeg's integer ("islow") IDCT, its h2v2
  * "fancy" chroma upsampling and its fixed-point colour conversion, on the
@@ -506,9 +531,15 @@ int mij_decoder_reconstruct(mij_decoder *d, int order);
 int mij_decoder_pixels(mij_decoder *d, int frame, uint8_t *dst, size_t cap, long long pitch);
 /* the IDCT output before upsampling: Y[w*h], Cb[w*h/4], Cr[w*h/4] */
 int mij_decoder_planes(mij_decoder *d, int frame, uint8_t *Y, uint8_t *Cb, uint8_t *Cr);
-/* device address of frame's pixels, packed rows (*pitch = 3*w, a multiple of
- * 16: usable with mij_batch_set_input); valid until the next decode.  The
- * pixels are complete once the decoder's stream has reached this point */
+/* host copy of component comp's padded sample plane after the IDCT (8 *
+ * blocks across bytes per row, 8 * blocks down rows), before upsampling:
+ * tells an IDCT error from an upsampling error; cap in bytes */
+int mij_decoder_plane(mij_decoder *d, int frame, int comp, uint8_t *dst, size_t cap);
+/* device address of frame's pixels, rows *pitch bytes apart: 3*w rounded up
+ * to 16 (for widths that are multiples of 16 that is 3*w, packed rows, usable
+ * with mij_batch_set_input); the bytes of a row past 3*w hold anything.
+ * Valid until the next decode.  The pixels are complete once the decoder's
+ * stream has reached this point */
 void *mij_decoder_device_pixels(mij_decoder *d, int frame, long long *pitch);
 /* HIP-event times of the last reconstruct: {dc + idct, colour}; waits */
 int mij_decoder_reconstruct_ms(mij_decoder *d, float ms[2]);

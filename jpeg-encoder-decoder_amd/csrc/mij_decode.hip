@@ -1,16 +1,25 @@
-// mij_decode.hip -- round-trip verifier: baseline JFIF -> quantized
-// coefficient planes on the GPU (the reference has
-// no decoder, func_tester.c:1262-1309 checks its output with libjpeg).
+// mij_decode.hip -- baseline JPEG decoder: streams -> quantized coefficient
+// planes -> pixels on the GPU (the reference has no
+// decoder, func_tester.c:1262-1309 checks its output with libjpeg).
 //
-// Scope: the streams this library and the reference write (encoder.c:549-644):
-// 8-bit baseline, 3 components Y 2x2 / Cb 1x1 / Cr 1x1, three
-// non-interleaved scans, no restart markers.  The output is the encoder's
-// own coefficient layout (encoder.c:158-178): per component, blocks in
-// raster order, 64 zigzag-ordered coefficients per block, the DC as the
-// coded difference -- so decode(encode(x)) can be compared bit-exactly with
-// rgb_to_dct(x) at any size.
+// Scope: baseline sequential DCT (SOF0, 8-bit, Huffman) in two shapes.
+// (a) The streams this library and the reference write (encoder.c:549-644):
+// 3 components Y 2x2 / Cb 1x1 / Cr 1x1, three non-interleaved scans, no
+// restart markers, sizes multiples of 16.  Their output is the encoder's own
+// coefficient layout (encoder.c:158-178): per component, blocks in raster
+// order, 64 zigzag-ordered coefficients per block, the DC as the coded
+// difference -- so decode(encode(x)) can be compared bit-exactly with
+// rgb_to_dct(x) at any size.  (b) What libjpeg, cameras and browsers write:
+// one interleaved scan (a greyscale file's single scan included), greyscale
+// or YCbCr with luma 1x1 / 2x1 / 2x2 and chroma 1x1, any size from 1x1,
+// arbitrary component ids, DQT ids 0..3, restart intervals.  Their planes are
+// padded to whole MCUs and live in an arena of their own (k_il_* kernels;
+// DESIGN.md "Decoding ordinary baseline files").  Refused with MIJ_EJPEG and
+// the reason: SOF1..15, 12-bit samples, 16-bit DQT, 2 or 4 components, Adobe
+// RGB / YCCK, other sampling, further scans, Ss/Se/AhAl other than 0/63/0,
+// missing tables, restart markers missing or out of order.
 //
-// Host: marker parsing (SOI, APP0, DQT, DHT, SOF0, SOS, EOI), canonical
+// Host: marker parsing (SOI, APPn, DQT, DHT, DRI, SOF0, SOS, EOI), canonical
 // Huffman tables with a 9-bit lookahead, and the scans copied unstuffed
 // into one pinned staging blob.  Device: every scan is cut into 512-bit
 // chunks, one lane per chunk.  Entropy decoding is sequential by
@@ -380,7 +389,8 @@ struct RecFrame {
 // each tile's base.  k_dec_idct adds the two.  All sums modulo 2^32.
 constexpr int DC_T = 1024, DC_PER = 8, DC_TILE = DC_T * DC_PER;
 
-__device__ __forceinline__ int rec_tile_job(const RecJob *jobs, int njobs, int tile) {
+template <class J>
+__device__ __forceinline__ int rec_tile_job(const J *jobs, int njobs, int tile) {
   int lo = 0, hi = njobs - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -427,7 +437,8 @@ __global__ __launch_bounds__(DC_T) void k_dec_dc(const RecJob *jobs, int njobs, 
 
 // tile totals -> exclusive prefix within each plane (a 3840x2160 luma plane
 // has 16 tiles)
-__global__ __launch_bounds__(64) void k_dec_dcbase(const RecJob *jobs, int njobs, uint32_t *tile) {
+template <class J>
+__global__ __launch_bounds__(64) void k_dec_dcbase(const J *jobs, int njobs, uint32_t *tile) {
   const int j = blockIdx.x * 64 + threadIdx.x;
   if (j >= njobs) return;
   const int t0 = jobs[j].tile0, nt = (jobs[j].nblocks + DC_TILE - 1) / DC_TILE;
@@ -439,7 +450,8 @@ __global__ __launch_bounds__(64) void k_dec_dcbase(const RecJob *jobs, int njobs
   }
 }
 
-__device__ __forceinline__ int rec_job_of(const RecJob *jobs, int njobs, int wg) {
+template <class J>
+__device__ __forceinline__ int rec_job_of(const J *jobs, int njobs, int wg) {
   int lo = 0, hi = njobs - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -484,7 +496,8 @@ __global__ __launch_bounds__(256) void k_dec_idct(const RecJob *jobs, int njobs,
     store_as(dst + r * pitch, W2{rows[r][0], rows[r][1]});
 }
 
-__device__ __forceinline__ int rec_frame_of(const RecFrame *fr, int n, int wg) {
+template <class F>
+__device__ __forceinline__ int rec_frame_of(const F *fr, int n, int wg) {
   int lo = 0, hi = n - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -508,6 +521,379 @@ __global__ __launch_bounds__(256) void k_dec_colour(const RecFrame *frames, int 
   colour_tile(Y, Cb, Cr, fr.w, fr.h, r, g, rgb, pix + fr.pix);
 }
 
+// ---------------------------------------------------------------------------
+// Interleaved scans (DESIGN.md "Decoding ordinary baseline files"): one scan
+// holds MCUs of up to 6 blocks, cut into restart intervals.  An interval is
+// what a scan is above: its own zero-padded slot of the blob, its own chunks,
+// an exact entry (first bit, k 0, slot 0) for its first chunk.  A chunk's
+// state is (bit position, coefficient index k, block slot within the MCU);
+// the Huffman tables follow the slot.
+//
+// Bounds, whatever the bits say.  Reads: a window is taken only at pos <
+// stop <= nbits and covers words pos/64 and pos/64 + 1, i.e. at most 15
+// bytes past the interval's last byte; every slot ends in >= 16 zero bytes.
+// States: k leaves a span in 0..63 (a run past 63 is "bad", ZRL / EOB end
+// the block), slot in 0..bpm-1 (only ever stepped modulo bpm), and a state
+// is only ever produced by these kernels.  Stores: k_il_write stores block
+// b of interval i only while b < nmcus_i * bpm, to MCU mcu0_i + b / bpm <
+// the frame's MCU count (the host checks mcu0_i + nmcus_i <= mcus_x *
+// mcus_y before any launch), at a position inside that MCU (slot_x < h_c,
+// slot_y < v_c), hence inside the component's padded plane; b itself comes
+// from the prefix sum and is checked >= 0 and congruent to the entry slot
+// first.  A stream that breaks any of this ends in a status code.
+// ---------------------------------------------------------------------------
+struct IlFrame {
+  long long off[3];  // first int16 of each component's padded plane
+  int ncomp, bpm;    // blocks per MCU
+  int mcus_x, nmcus;
+  int chunk0, nchunks;  // all chunks of the frame's intervals, contiguous
+  int hs[3], vs[3], bw[3];
+  int dc[3], ac[3];  // table indices per component
+  int slot_comp[6], slot_x[6], slot_y[6];
+};
+
+struct IlJob {          // one restart interval (a whole scan without DRI)
+  long long data, nbits;  // as DecJob
+  int frame;            // index into the IlFrame table
+  int mcu0, nmcus;
+  int chunk0, nchunks;
+  int pad;
+};
+
+struct IlArgs {
+  const uint8_t *blob;
+  const IlJob *jobs;
+  const IlFrame *frames;
+  int njobs, nchunks;
+  const DecTab *tabs;
+  long long *entry_pos, *exit_in, *exit_out;  // (pos * 8 + slot) * 64 + k
+  int *nblk;
+  int *changed;
+  int first;
+};
+
+__device__ __forceinline__ long long il_pack(long long pos, int slot, int k) { return (pos * 8 + slot) * 64 + k; }
+
+__device__ __forceinline__ int il_job_of(const IlJob *jobs, int njobs, int c) {
+  int lo = 0, hi = njobs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (jobs[mid].chunk0 <= c) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// k_dec_sync for intervals: the same passes, the state one field wider.  A
+// chunk decodes again only when its predecessor's exit state, slot included,
+// changed.
+__global__ __launch_bounds__(256) void k_il_sync(IlArgs a) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= a.nchunks) return;
+  const IlJob &job = a.jobs[il_job_of(a.jobs, a.njobs, c)];
+  const int lc = c - job.chunk0;
+  long long entry;
+  if (a.first || lc == 0) {
+    entry = il_pack((long long)lc * CHUNK, 0, 0);
+    if (!a.first) {
+      a.exit_out[c] = a.exit_in[c];
+      return;
+    }
+  } else {
+    entry = a.exit_in[c - 1];
+    if (entry < 0) entry = il_pack((long long)lc * CHUNK, 0, 0);  // predecessor met a bad code
+    if (entry == a.entry_pos[c]) {
+      a.exit_out[c] = a.exit_in[c];
+      return;
+    }
+    *a.changed = 1;
+  }
+  a.entry_pos[c] = entry;
+  const IlFrame &F = a.frames[job.frame];
+  Bits br{(const unsigned long long *)(a.blob + job.data)};
+  long long pos = entry >> 9;
+  int slot = (int)(entry >> 6) & 7, k = (int)(entry & 63);
+  const long long stop = min((long long)(lc + 1) * CHUNK, job.nbits);
+  long long blocks_left = (long long)job.nmcus * F.bpm;
+  int comp = F.slot_comp[slot];
+  const DecTab *dc = a.tabs + F.dc[comp], *ac = a.tabs + F.ac[comp];
+  int started = 0;
+  bool bad = false;
+  while (pos < stop) {
+    int sym, val;
+    if (k == 0) {
+      if (blocks_left <= 0) break;
+      const int n = decode_one(br, pos, *dc, sym, val);
+      if (!n || sym > 15) {
+        bad = true;
+        break;
+      }
+      pos += n;
+      started++;
+      k = 1;
+    } else {
+      const int n = decode_one(br, pos, *ac, sym, val);
+      if (!n) {
+        bad = true;
+        break;
+      }
+      pos += n;
+      const int r = sym >> 4;
+      if (sym & 15) {
+        k += r;
+        if (k > 63) {
+          bad = true;
+          break;
+        }
+        k++;
+      } else {
+        k = r == 15 ? k + 16 : 64;  // ZRL / EOB
+      }
+    }
+    if (k >= 64) {
+      k = 0;
+      blocks_left--;
+      slot = slot + 1 == F.bpm ? 0 : slot + 1;
+      comp = F.slot_comp[slot];
+      dc = a.tabs + F.dc[comp];
+      ac = a.tabs + F.ac[comp];
+    }
+  }
+  a.nblk[c] = started;
+  a.exit_out[c] = bad ? -1 : il_pack(pos, slot, k);
+}
+
+// per frame (not per interval: a file may hold thousands of one-MCU
+// intervals): exclusive scan of its chunks' block counts across all its
+// intervals.  k_il_write takes differences against its interval's first chunk.
+__global__ __launch_bounds__(256) void k_il_scan(const IlFrame *frames, const int *nblk, long long *base) {
+  __shared__ long long part[256];
+  const int chunk0 = frames[blockIdx.x].chunk0, nchunks = frames[blockIdx.x].nchunks;
+  long long carry = 0;
+  for (int t0 = 0; t0 < nchunks; t0 += 256) {
+    const int t = t0 + threadIdx.x;
+    const long long v = t < nchunks ? nblk[chunk0 + t] : 0;
+    part[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+      const long long add = threadIdx.x >= o ? part[threadIdx.x - o] : 0;
+      __syncthreads();
+      part[threadIdx.x] += add;
+      __syncthreads();
+    }
+    if (t < nchunks) base[chunk0 + t] = carry + part[threadIdx.x] - v;
+    const long long tot = part[255];
+    __syncthreads();
+    carry += tot;
+  }
+}
+
+// k_dec_write for intervals.  Scan-order block b of the interval lies in MCU
+// mcu0 + b / bpm at slot b % bpm; its place is that component's padded plane,
+// block row my * v_c + slot_y, block column mx * h_c + slot_x.  status: one
+// int per frame; 5 = an interval holds fewer blocks than its MCUs need, 6 =
+// invalid code, 7 = the prefix sum and the settled slot disagree.
+__global__ __launch_bounds__(256) void k_il_write(IlArgs a, const long long *base, int16_t *coefs, int *status) {
+  __shared__ int4 slotbuf[256][8];
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= a.nchunks) return;
+  const IlJob &job = a.jobs[il_job_of(a.jobs, a.njobs, c)];
+  const IlFrame &F = a.frames[job.frame];
+  const int lc = c - job.chunk0;
+  const long long nblocks = (long long)job.nmcus * F.bpm;
+  const long long lb = base[c] - base[job.chunk0];  // blocks the interval's earlier chunks started
+  if (lc == job.nchunks - 1 && lb + a.nblk[c] < nblocks) atomicMax(&status[job.frame], 5);
+  const long long entry = a.entry_pos[c];
+  long long pos = entry >> 9;
+  int slot = (int)(entry >> 6) & 7, k = (int)(entry & 63);
+  // the block in progress at the entry was started by an earlier chunk
+  long long blk = lb - (k ? 1 : 0);
+  if (blk >= nblocks) return;  // pad bits after the last block
+  if (blk < 0 || (int)(blk % F.bpm) != slot) {
+    atomicMax(&status[job.frame], 7);
+    return;
+  }
+  int mcu = job.mcu0 + (int)(blk / F.bpm);
+  Bits br{(const unsigned long long *)(a.blob + job.data)};
+  const long long stop = min((long long)(lc + 1) * CHUNK, job.nbits);
+  int4 *sl = slotbuf[threadIdx.x];
+  int16_t *b16 = (int16_t *)sl;
+#pragma unroll
+  for (int q = 0; q < 8; q++) sl[q] = int4{0, 0, 0, 0};
+  int first = k;
+  bool bad = false;
+  while (pos < stop && blk < nblocks) {
+    const int comp = F.slot_comp[slot];
+    int sym, val;
+    const int n = decode_one(br, pos, a.tabs[k ? F.ac[comp] : F.dc[comp]], sym, val);
+    if (!n) {
+      bad = true;
+      break;
+    }
+    pos += n;
+    if (k == 0) {
+      if (sym > 15) {
+        bad = true;
+        break;
+      }
+      b16[0] = (int16_t)val;
+      k = 1;
+    } else {
+      const int r = sym >> 4;
+      if (sym & 15) {
+        k += r;
+        if (k > 63) {
+          bad = true;
+          break;
+        }
+        b16[k++] = (int16_t)val;
+      } else {
+        k = r == 15 ? k + 16 : 64;  // ZRL / EOB
+      }
+    }
+    if (k >= 64) {  // block complete: store it, clear the slot
+      const int my = mcu / F.mcus_x, mx = mcu - my * F.mcus_x;
+      int16_t *o = coefs + F.off[comp] +
+                   64 * ((long long)(my * F.vs[comp] + F.slot_y[slot]) * F.bw[comp] + mx * F.hs[comp] + F.slot_x[slot]);
+      if (first == 0) {
+#pragma unroll
+        for (int q = 0; q < 8; q++) ((int4 *)o)[q] = sl[q];
+      } else {
+        for (int t = first; t < 64; t++) o[t] = b16[t];
+      }
+#pragma unroll
+      for (int q = 0; q < 8; q++) sl[q] = int4{0, 0, 0, 0};
+      first = 0;
+      k = 0;
+      blk++;
+      if (++slot == F.bpm) {
+        slot = 0;
+        mcu++;
+      }
+    }
+  }
+  if (!bad && k && blk < nblocks) {  // block continues in the next chunk
+    const int comp = F.slot_comp[slot];
+    const int my = mcu / F.mcus_x, mx = mcu - my * F.mcus_x;
+    int16_t *o = coefs + F.off[comp] +
+                 64 * ((long long)(my * F.vs[comp] + F.slot_y[slot]) * F.bw[comp] + mx * F.hs[comp] + F.slot_x[slot]);
+    for (int t = first; t < k; t++) o[t] = b16[t];
+  }
+  if (bad) atomicMax(&status[job.frame], 6);
+}
+
+// Reconstruction for these frames.  DC prediction runs per component in scan
+// order (inside an MCU left-right, top-bottom, then the next MCU) and starts
+// again at 0 every restart interval, i.e. every `seg` blocks of the
+// component.  k_il_dc is k_dec_dc over scan-order index s instead of raster
+// order: dc[off / 64 + s] = the sum of differences 0..s relative to the tile,
+// tile totals as before, k_dec_dcbase unchanged.  With P(s) = dc + tile base,
+// block s has absolute DC P(s) - P(first block of its segment - 1): two loads
+// in k_il_idct, no segmented scan.  All modulo 2^32.
+struct IlRec {      // one component of one frame
+  long long off;    // as RecJob
+  int nblocks, bw;  // padded plane: blocks, and blocks per row (mcus_x * h_c)
+  int wg0, qt, tile0;
+  int hs, vs, mcus_x;
+  int seg;          // blocks between DC resets: Ri * h_c * v_c, nblocks without DRI
+  int pad;
+};
+
+// scan-order index -> raster index in the padded plane, and back
+__device__ __forceinline__ int il_raster(const IlRec &j, int s) {
+  const int hv = j.hs * j.vs, m = s / hv, i = s - m * hv;
+  const int my = m / j.mcus_x, mx = m - my * j.mcus_x, iy = i / j.hs, ix = i - iy * j.hs;
+  return (my * j.vs + iy) * j.bw + mx * j.hs + ix;
+}
+__device__ __forceinline__ int il_scan_index(const IlRec &j, int blk) {
+  const int by = blk / j.bw, bx = blk - by * j.bw;
+  const int my = by / j.vs, iy = by - my * j.vs, mx = bx / j.hs, ix = bx - mx * j.hs;
+  return (my * j.mcus_x + mx) * (j.hs * j.vs) + iy * j.hs + ix;
+}
+
+__global__ __launch_bounds__(DC_T) void k_il_dc(const IlRec *jobs, int njobs, const int16_t *coefs, int32_t *dc,
+                                                uint32_t *tile) {
+  __shared__ uint32_t wsum[DC_T / 64];
+  const IlRec job = jobs[rec_tile_job(jobs, njobs, blockIdx.x)];
+  const int16_t *src = coefs + job.off;
+  int32_t *dst = dc + job.off / 64;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b0 = ((int)blockIdx.x - job.tile0) * DC_TILE + (int)threadIdx.x * DC_PER;
+  uint32_t v[DC_PER], s = 0;
+#pragma unroll
+  for (int i = 0; i < DC_PER; i++) {
+    if (b0 + i < job.nblocks) s += (uint32_t)(int32_t)src[64LL * il_raster(job, b0 + i)];
+    v[i] = s;
+  }
+  uint32_t x = s;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  if (lane == 63) wsum[wave] = x;
+  __syncthreads();
+  uint32_t base = x - s, tot = 0;
+#pragma unroll
+  for (int k = 0; k < DC_T / 64; k++) {
+    const uint32_t t = wsum[k];
+    if (k < wave) base += t;
+    tot += t;
+  }
+#pragma unroll
+  for (int i = 0; i < DC_PER; i++)
+    if (b0 + i < job.nblocks) dst[b0 + i] = (int32_t)(base + v[i]);
+  if (threadIdx.x == 0) tile[blockIdx.x] = tot;
+}
+
+// k_dec_idct with the component's own quantiser and the DC rule above
+__global__ __launch_bounds__(256) void k_il_idct(const IlRec *jobs, int njobs, const int16_t *coefs, const int32_t *dc,
+                                                 const uint32_t *tile, const int32_t *q, uint8_t *planes) {
+  __shared__ int4 stage[256 * 9];
+  const IlRec job = jobs[rec_job_of(jobs, njobs, blockIdx.x)];
+  const int first = ((int)blockIdx.x - job.wg0) * 256;
+  const int nb = min(256, job.nblocks - first);
+  const int4 *src = (const int4 *)(coefs + job.off + 64LL * first);
+  for (int i = threadIdx.x; i < nb * 8; i += 256) stage[(i >> 3) * 9 + (i & 7)] = src[i];
+  __syncthreads();
+  if ((int)threadIdx.x >= nb) return;
+  const int blk = first + threadIdx.x;
+  union {
+    int4 v[8];
+    int16_t c[64];
+  } in;
+#pragma unroll
+  for (int k = 0; k < 8; k++) in.v[k] = stage[threadIdx.x * 9 + k];
+  const int s = il_scan_index(job, blk), s0 = s / job.seg * job.seg;
+  const int32_t *pd = dc + job.off / 64;
+  uint32_t dc_abs = (uint32_t)pd[s] + tile[job.tile0 + s / DC_TILE];
+  if (s0 > 0) dc_abs -= (uint32_t)pd[s0 - 1] + tile[job.tile0 + (s0 - 1) / DC_TILE];
+  uint32_t rows[8][2];
+  idct_block(in.c, dc_abs, q + 64 * job.qt, rows);
+  const int by = blk / job.bw, bx = blk - by * job.bw;
+  const long long pitch = 8LL * job.bw;
+  uint8_t *dst = planes + job.off + 8LL * by * pitch + 8 * bx;
+#pragma unroll
+  for (int r = 0; r < 8; r++) store_as(dst + r * pitch, W2{rows[r][0], rows[r][1]});
+}
+
+struct IlPix {
+  long long y, cb, cr;  // first byte of each padded sample plane
+  long long pix;        // first byte of the pixels, rows G.pitch apart
+  PixGeom G;
+  int groups, units;    // 16-pixel groups per row; rows or row pairs (colour_tile_any)
+  int wg0, pad;
+};
+
+__global__ __launch_bounds__(256) void k_il_colour(const IlPix *frames, int nframes, const uint8_t *planes,
+                                                   uint8_t *pix, int rgb) {
+  const IlPix fr = frames[rec_frame_of(frames, nframes, blockIdx.x)];
+  const long long idx = ((long long)blockIdx.x - fr.wg0) * 256 + (int)threadIdx.x;
+  if (idx >= (long long)fr.units * fr.groups) return;
+  const int u = (int)(idx / fr.groups), g = (int)(idx - (long long)u * fr.groups);
+  colour_tile_any(planes + fr.y, planes + fr.cb, planes + fr.cr, fr.G, u, g, rgb, pix + fr.pix);
+}
+
 }  // namespace mij
 
 // ---------------------------------------------------------------------------
@@ -517,16 +903,37 @@ namespace {
 
 struct Parsed {
   int w = 0, h = 0;
-  uint8_t dqt[2][64];
-  bool have_dqt[2] = {false, false};
-  mij::DecTab tab[4];  // DC0, AC0 (luma), DC1, AC1 (chroma): index 2*Th + Tc
+  int ncomp = 0;
+  // components in SOF order; a single component is 1x1 whatever it declares
+  int cid[3] = {0, 0, 0}, hs[3] = {1, 1, 1}, vs[3] = {1, 1, 1}, tq[3] = {0, 0, 0};
+  int hmax = 1, vmax = 1, mcus_x = 0, mcus_y = 0;
+  int bw[3] = {0, 0, 0}, bh[3] = {0, 0, 0};  // padded planes, in blocks
+  int ri = 0;       // restart interval in MCUs, 0 = none
+  int adobe = -1;   // APP14 transform, -1 = no such segment
+  bool legacy = false;       // the encoder's shape: three one-component scans, 4:2:0, multiples of 16
+  bool interleaved = false;  // one scan holding every component
+  uint8_t dqt[4][64];
+  bool have_dqt[4] = {false, false, false, false};
+  mij::DecTab tab[4];  // DC0, AC0, DC1, AC1: index 2*Th + Tc
   bool have_tab[4] = {false, false, false, false};
   struct Scan {
     int comp, td, ta;
     long long data, end;
-  } scan[3];
+  } scan[3];        // legacy: the three scans
   int nscans = 0;
   int comp_seen = 0;  // components that already have a scan (bit c)
+  int td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};  // interleaved: tables per component
+  struct Ivl {
+    long long data, end;  // raw bytes of one restart interval
+  };
+  std::vector<Ivl> ivl;
+  char err[200] = "";
+  long long units() const {  // int16 coefficients == sample bytes of all padded planes
+    long long u = 0;
+    for (int c = 0; c < ncomp; c++) u += 64LL * bw[c] * bh[c];
+    return u;
+  }
+  long long pitch() const { return (3LL * w + 15) / 16 * 16; }
 };
 
 int be16(const uint8_t *p) { return (p[0] << 8) | p[1]; }
@@ -552,8 +959,14 @@ int build_table(mij::DecTab &t, const uint8_t counts[16], const uint8_t *syms, i
   return 0;
 }
 
+// Host only (no device use): the message goes to P.err, since streams are
+// parsed on worker threads; the caller reports it.
 int parse(const uint8_t *s, size_t n, Parsed &P, int frame) {
-#define BAD(...) return mij_fail(MIJ_EJPEG, __VA_ARGS__)
+#define BAD(...)                                  \
+  do {                                            \
+    snprintf(P.err, sizeof P.err, __VA_ARGS__);   \
+    return MIJ_EJPEG;                             \
+  } while (0)
   if (n < 4 || s[0] != 0xFF || s[1] != 0xD8) BAD("stream %d: no SOI", frame);
   size_t i = 2;
   while (i + 4 <= n) {
@@ -564,14 +977,16 @@ int parse(const uint8_t *s, size_t n, Parsed &P, int frame) {
       continue;
     }
     if (m == 0xD9) break;  // EOI
+    if (m >= 0xD0 && m <= 0xD7) BAD("stream %d: restart marker RST%d without a restart interval in force", frame, m - 0xD0);
     const int len = be16(s + i + 2);
     if (len < 2 || i + 2 + len > n) BAD("stream %d: segment 0x%02X length %d", frame, m, len);
     const uint8_t *q = s + i + 4;
     const int body = len - 2;
     if (m == 0xDB) {  // DQT, 8-bit, possibly several tables
-      for (int o = 0; o + 65 <= body; o += 65) {
+      for (int o = 0; o < body; o += 65) {
         const int tq = q[o] & 15;
-        if ((q[o] >> 4) || tq > 1) BAD("stream %d: DQT Pq/Tq %02X", frame, q[o]);
+        if (q[o] >> 4) BAD("stream %d: 16-bit DQT (Pq %d) is not baseline 8-bit", frame, q[o] >> 4);
+        if (tq > 3 || o + 65 > body) BAD("stream %d: DQT Tq %d / length", frame, tq);
         memcpy(P.dqt[tq], q + o + 1, 64);
         P.have_dqt[tq] = true;
       }
@@ -589,60 +1004,178 @@ int parse(const uint8_t *s, size_t n, Parsed &P, int frame) {
         o += 17 + nsym;
       }
     } else if (m == 0xC0) {  // SOF0
-      if (body < 15 || q[0] != 8 || q[5] != 3) BAD("stream %d: SOF0 not 8-bit 3-component", frame);
+      if (P.ncomp) BAD("stream %d: second SOF0", frame);
+      if (body < 6) BAD("stream %d: SOF0 length", frame);
+      if (q[0] != 8) BAD("stream %d: %d-bit samples (only 8-bit)", frame, q[0]);
+      const int nc = q[5];
+      if (nc != 1 && nc != 3) BAD("stream %d: %d components (only greyscale and YCbCr)", frame, nc);
+      if (body < 6 + 3 * nc) BAD("stream %d: SOF0 length", frame);
       P.h = be16(q + 1);
       P.w = be16(q + 3);
-      const uint8_t want[3][3] = {{1, 0x22, 0}, {2, 0x11, 1}, {3, 0x11, 1}};
-      for (int c = 0; c < 3; c++)
-        if (memcmp(q + 6 + 3 * c, want[c], 3)) BAD("stream %d: SOF0 component %d is not 4:2:0", frame, c);
-      if (P.w <= 0 || P.h <= 0 || P.w % 16 || P.h % 16) BAD("stream %d: %dx%d", frame, P.w, P.h);
+      if (P.w <= 0 || P.h <= 0) BAD("stream %d: %dx%d", frame, P.w, P.h);
+      for (int c = 0; c < nc; c++) {
+        const uint8_t *e = q + 6 + 3 * c;
+        P.cid[c] = e[0];
+        P.hs[c] = e[1] >> 4;
+        P.vs[c] = e[1] & 15;
+        P.tq[c] = e[2];
+        if (P.hs[c] < 1 || P.hs[c] > 4 || P.vs[c] < 1 || P.vs[c] > 4 || P.tq[c] > 3)
+          BAD("stream %d: SOF0 component %d sampling %dx%d / Tq %d", frame, c, P.hs[c], P.vs[c], P.tq[c]);
+        for (int b = 0; b < c; b++)
+          if (P.cid[b] == P.cid[c]) BAD("stream %d: SOF0 repeats component id %d", frame, P.cid[c]);
+      }
+      if (nc == 1) {
+        P.hs[0] = P.vs[0] = 1;
+      } else {
+        if (P.hs[1] != 1 || P.vs[1] != 1 || P.hs[2] != 1 || P.vs[2] != 1)
+          BAD("stream %d: chroma sampling %dx%d / %dx%d (only 1x1)", frame, P.hs[1], P.vs[1], P.hs[2], P.vs[2]);
+        if (!(P.hs[0] <= 2 && P.vs[0] <= P.hs[0]))
+          BAD("stream %d: luma sampling %dx%d (only 1x1, 2x1, 2x2)", frame, P.hs[0], P.vs[0]);
+      }
+      P.ncomp = nc;
+      P.hmax = P.hs[0];
+      P.vmax = P.vs[0];
+      P.mcus_x = (P.w + 8 * P.hmax - 1) / (8 * P.hmax);
+      P.mcus_y = (P.h + 8 * P.vmax - 1) / (8 * P.vmax);
+      for (int c = 0; c < nc; c++) {
+        P.bw[c] = P.mcus_x * P.hs[c];
+        P.bh[c] = P.mcus_y * P.vs[c];
+      }
     } else if (m == 0xC1 || m == 0xC2 || m == 0xC3 || (m >= 0xC5 && m <= 0xCF && m != 0xC8 && m != 0xCC)) {
       BAD("stream %d: SOF 0x%02X is not baseline", frame, m);
+    } else if (m == 0xDD) {  // DRI
+      if (body != 2) BAD("stream %d: DRI length", frame);
+      P.ri = be16(q);
+    } else if (m == 0xEE) {  // APP14: Adobe's colour transform flag
+      if (body >= 12 && !memcmp(q, "Adobe", 5)) P.adobe = q[11];
     } else if (m == 0xDA) {  // SOS + entropy data
-      if (P.nscans >= 3 || body < 6 || q[0] != 1) BAD("stream %d: SOS (only 1-component scans)", frame);
-      if (q[3] != 0 || q[4] != 63 || q[5] != 0) BAD("stream %d: SOS Ss/Se/AhAl", frame);
-      Parsed::Scan &sc = P.scan[P.nscans++];
-      sc.comp = q[1] - 1;
-      sc.td = q[2] >> 4;
-      sc.ta = q[2] & 15;
-      if (sc.comp < 0 || sc.comp > 2 || sc.td > 1 || sc.ta > 1) BAD("stream %d: SOS component", frame);
-      // each component exactly once: a repeated scan would leave another
-      // component's plane unwritten (it keeps the previous call's values)
-      if (P.comp_seen & (1 << sc.comp)) BAD("stream %d: SOS repeats component %d", frame, sc.comp + 1);
-      P.comp_seen |= 1 << sc.comp;
+      if (!P.ncomp) BAD("stream %d: SOS before SOF0", frame);
+      if (body < 1 || body != 4 + 2 * q[0]) BAD("stream %d: SOS length", frame);
+      const int ns = q[0];
+      const uint8_t *tail = q + 1 + 2 * ns;
+      if (tail[0] != 0 || tail[1] != 63 || tail[2] != 0) BAD("stream %d: SOS Ss/Se/AhAl (only 0, 63, 0)", frame);
+      if (P.interleaved) BAD("stream %d: more than one scan after an interleaved scan", frame);
+      const bool il = ns == P.ncomp;
+      if (il) {
+        if (P.nscans) BAD("stream %d: interleaved scan after one-component scans", frame);
+        for (int c = 0; c < ns; c++) {
+          if (q[1 + 2 * c] != P.cid[c]) BAD("stream %d: SOS selectors are not the SOF0 components in order", frame);
+          P.td[c] = q[2 + 2 * c] >> 4;
+          P.ta[c] = q[2 + 2 * c] & 15;
+          if (P.td[c] > 1 || P.ta[c] > 1) BAD("stream %d: SOS table ids", frame);
+          if (!P.have_tab[2 * P.td[c]] || !P.have_tab[2 * P.ta[c] + 1])
+            BAD("stream %d: Huffman table of component %d missing before its scan", frame, c);
+        }
+        P.interleaved = true;
+      } else {
+        // one-component scans: only the encoder's own shape.  Such scans of
+        // other samplings or sizes cover ceil(w_c / 8) x ceil(h_c / 8) blocks,
+        // not the padded plane, and nothing at hand writes them to test with.
+        if (ns != 1 || P.ncomp != 3 || P.hs[0] != 2 || P.vs[0] != 2 || P.w % 16 || P.h % 16 || P.ri ||
+            P.tq[1] != P.tq[2])
+          BAD("stream %d: SOS of %d components in a %d-component %dx%d frame (non-interleaved scans only as three "
+              "scans of a 4:2:0 frame, multiples of 16, no restarts)", frame, ns, P.ncomp, P.w, P.h);
+        if (P.nscans >= 3) BAD("stream %d: more than three scans", frame);
+        Parsed::Scan &sc = P.scan[P.nscans++];
+        sc.comp = -1;
+        for (int c = 0; c < 3; c++)
+          if (q[1] == P.cid[c]) sc.comp = c;
+        sc.td = q[2] >> 4;
+        sc.ta = q[2] & 15;
+        if (sc.comp < 0 || sc.td > 1 || sc.ta > 1) BAD("stream %d: SOS component", frame);
+        // each component exactly once: a repeated scan would leave another
+        // component's plane unwritten (it keeps the previous call's values)
+        if (P.comp_seen & (1 << sc.comp)) BAD("stream %d: SOS repeats component %d", frame, sc.comp + 1);
+        P.comp_seen |= 1 << sc.comp;
+      }
       size_t e = i + 2 + len;
-      sc.data = (long long)e;
+      long long start = (long long)e;
+      const long long nm = (long long)P.mcus_x * P.mcus_y;
+      const long long want = il && P.ri ? (nm + P.ri - 1) / P.ri : 1;
       // entropy data ends at the next marker: a 0xFF followed by neither
-      // 0x00 (stuffing) nor 0xFF.  The end-of-scan pad byte is never
-      // stuffed (encoder.c:425-432), so "FF FF xx" is a pad byte that still
-      // holds the scan's last bits, then the marker: it is kept as data.
+      // 0x00 (stuffing) nor 0xFF.  The reference never stuffs its end-of-scan
+      // pad byte (encoder.c:425-432), so "FF FF xx" is a pad byte that still
+      // holds the scan's last bits, then the marker: the first FF is kept as
+      // data.  On a standard stream those are fill bytes before a marker;
+      // kept, they are trailing one-bits after the last block, and decoding
+      // stops at the block count, so the same rule serves every stream.
+      // FF D0..D7 bound an interval only while a restart interval is in
+      // force; otherwise they end the scan and the marker loop refuses them.
       for (;;) {
         const uint8_t *f = (const uint8_t *)memchr(s + e, 0xFF, n - e);
-        if (!f || (size_t)(f - s) + 1 >= n) BAD("stream %d: scan %d runs to the end", frame, P.nscans);
+        if (!f || (size_t)(f - s) + 1 >= n) BAD("stream %d: scan %d runs to the end", frame, P.nscans + (il ? 1 : 0));
         e = f - s;
-        if (s[e + 1] == 0x00) {
+        const int b = s[e + 1];
+        if (b == 0x00) {
           e += 2;
           continue;
         }
-        if (s[e + 1] == 0xFF) {
+        if (b == 0xFF) {
           e += 1;
+          continue;
+        }
+        if (b >= 0xD0 && b <= 0xD7 && il && P.ri) {
+          const int k = (int)P.ivl.size();
+          if (b != 0xD0 + (k & 7))
+            BAD("stream %d: restart marker RST%d where RST%d is due (interval %d)", frame, b - 0xD0, k & 7, k);
+          if (k + 1 >= want) BAD("stream %d: more restart markers than its %lld intervals need", frame, want);
+          P.ivl.push_back({start, (long long)e});
+          e += 2;
+          start = (long long)e;
           continue;
         }
         break;
       }
-      sc.end = (long long)e;
+      if (il) {
+        P.ivl.push_back({start, (long long)e});
+        if ((long long)P.ivl.size() != want)
+          BAD("stream %d: %zu restart intervals, %lld expected (%lld MCUs, interval %d)", frame, P.ivl.size(), want,
+              nm, P.ri);
+      } else {
+        P.scan[P.nscans - 1].data = start;
+        P.scan[P.nscans - 1].end = (long long)e;
+      }
       i = e;
       continue;
     }
     i += 2 + len;  // APPn, COM, anything else: skipped
   }
-  if (!P.w || P.nscans != 3) BAD("stream %d: missing SOF0 or scans (%d)", frame, P.nscans);
+  if (!P.ncomp) BAD("stream %d: no SOF0", frame);
+  // Adobe transform 0 on three components is RGB, 2 is YCCK; on a single
+  // component the flag says nothing
+  if (P.ncomp == 3 && (P.adobe == 0 || P.adobe == 2))
+    BAD("stream %d: Adobe APP14 transform %d (RGB / YCCK), only YCbCr", frame, P.adobe);
+  if (P.interleaved) {
+    for (int c = 0; c < P.ncomp; c++)
+      if (!P.have_dqt[P.tq[c]]) BAD("stream %d: DQT %d of component %d missing", frame, P.tq[c], c);
+    return MIJ_OK;
+  }
+  if (P.nscans != 3) BAD("stream %d: missing scans (%d)", frame, P.nscans);
   for (int k = 0; k < 3; k++) {
     const auto &sc = P.scan[k];
     if (!P.have_tab[2 * sc.td] || !P.have_tab[2 * sc.ta + 1]) BAD("stream %d: scan %d table missing", frame, k);
   }
+  P.legacy = true;
   return MIJ_OK;
 #undef BAD
+}
+
+// where a frame of the last decode lives
+struct FrameLoc {
+  bool foreign = false;  // in the arena of padded planes, not in its legacy slot
+  long long off[3] = {0, 0, 0};  // first int16 / sample byte of each component's plane
+  long long pix = 0;     // first byte of its pixels (legacy: d_pix, else f_pix)
+};
+
+template <class T>
+int grow(T *&p, size_t &cap, size_t need) {
+  if (need <= cap) return MIJ_OK;
+  hipFree(p);  // waits for the device
+  p = nullptr;
+  cap = 0;
+  HIP_TRY(hipMalloc((void **)&p, need * sizeof(T)));
+  cap = need;
+  return MIJ_OK;
 }
 
 }  // namespace
@@ -662,10 +1195,11 @@ struct mij_decoder {
   int *d_nblk = nullptr;
   int chunk_cap = 0, job_cap = 1 << 30, last_passes = 0;
   std::vector<Parsed> parsed;
+  std::vector<FrameLoc> loc;
   long long plane_px = 0;  // max_w * max_h: Y plane; Cb/Cr a quarter each
   int n = 0;
   // pixels (mij_decoder_reconstruct): allocated on its first call
-  bool rec_ready = false;  // buffers and events exist
+  bool rec_ready = false;  // the legacy frames' buffers exist
   bool rec_valid = false;  // they hold the last decode's frames
   uint8_t *d_planes = nullptr, *d_pix = nullptr;
   int32_t *d_dc = nullptr, *d_recq = nullptr;
@@ -676,6 +1210,25 @@ struct mij_decoder {
   std::vector<mij::RecFrame> h_rframes;
   std::vector<int32_t> h_recq;
   hipEvent_t rec_ev[3] = {nullptr, nullptr, nullptr};
+  // Frames that are not of the legacy shape live in an arena of their own,
+  // packed frame after frame in the order of the call and grown (freed and
+  // allocated again) when a call needs more: a decoder that only ever sees
+  // legacy streams allocates none of it.
+  int16_t *f_coef = nullptr;
+  uint8_t *f_planes = nullptr, *f_pix = nullptr;
+  int32_t *f_dc = nullptr, *f_recq = nullptr;
+  uint32_t *f_tile = nullptr;
+  mij::IlJob *f_jobs = nullptr;
+  mij::IlFrame *f_frames = nullptr;
+  int *f_status = nullptr;
+  mij::IlRec *f_rjobs = nullptr;
+  mij::IlPix *f_rpix = nullptr;
+  size_t f_coef_cap = 0, f_planes_cap = 0, f_pix_cap = 0, f_dc_cap = 0, f_recq_cap = 0, f_tile_cap = 0,
+         f_jobs_cap = 0, f_frames_cap = 0, f_status_cap = 0, f_rjobs_cap = 0, f_rpix_cap = 0;
+  long long f_pix_bytes = 0;  // of the last decode's frames
+  std::vector<mij::IlRec> h_irec;
+  std::vector<mij::IlPix> h_ipix;
+  std::vector<int32_t> h_irecq;
 };
 
 static void decoder_free(mij_decoder *d) {
@@ -700,6 +1253,17 @@ static void decoder_free(mij_decoder *d) {
   hipFree(d->d_tile);
   hipFree(d->d_rjobs);
   hipFree(d->d_rframes);
+  hipFree(d->f_coef);
+  hipFree(d->f_planes);
+  hipFree(d->f_pix);
+  hipFree(d->f_dc);
+  hipFree(d->f_recq);
+  hipFree(d->f_tile);
+  hipFree(d->f_jobs);
+  hipFree(d->f_frames);
+  hipFree(d->f_status);
+  hipFree(d->f_rjobs);
+  hipFree(d->f_rpix);
   for (hipEvent_t e : d->rec_ev)
     if (e) hipEventDestroy(e);
   if (d->h_blob) hipHostFree(d->h_blob);
@@ -757,8 +1321,6 @@ static int decoder_stage(mij_decoder *d, size_t total) {
   return MIJ_OK;
 }
 
-// Parses n streams, stages them in one device blob and decodes every scan.
-// Synchronous; the coefficients stay on the device (mij_decoder_coefs).
 // Unstuffed copy of scan bytes [b, e) of stream s into dst; returns bytes
 static size_t unstuff(uint8_t *dst, const uint8_t *s, size_t b, size_t e) {
   size_t o = 0;
@@ -793,82 +1355,15 @@ static int decoder_buffers(mij_decoder *d, int nchunks, int njobs) {
   return MIJ_OK;
 }
 
-// Parses n streams, stages their unstuffed scans in one device blob and
-// decodes every scan chunk-parallel.  Synchronous; the coefficients stay on
-// the device (mij_decoder_coefs).
-extern "C" int mij_decoder_decode(mij_decoder *d, const uint8_t *const *jpgs, const size_t *lens, int n) {
-  mij_clear_error();
-  if (!d || !jpgs || !lens || n < 1 || n > d->cap) return mij_fail(MIJ_EINVAL, "decoder_decode: bad args");
-  HIP_TRY(hipSetDevice(d->dev));
-  d->n = 0;  // set to n only once every stream decoded cleanly
-  d->rec_valid = false;  // pixels of an earlier decode are no longer served
-  d->parsed.assign(n, Parsed());
-  // host work per stream in parallel: parse (finds the scan ends), then
-  // unstuff each scan into its slot (sized by the raw length, an upper bound)
-  const int nth = std::max(1, std::min(n, (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()))));
-  auto parallel = [&](auto &&fn) {
-    std::atomic<int> next{0};
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nth; t++)
-      pool.emplace_back([&] { for (int f; (f = next++) < n;) fn(f); });
-    for (int f; (f = next++) < n;) fn(f);
-    for (auto &th : pool) th.join();
-  };
-  std::vector<int> prc(n, MIJ_OK);
-  for (int f = 0; f < n; f++)
-    if (!jpgs[f]) return mij_fail(MIJ_EINVAL, "decoder_decode: stream %d is NULL", f);
-  parallel([&](int f) { prc[f] = parse(jpgs[f], lens[f], d->parsed[f], f); });
-  for (int f = 0; f < n; f++) {
-    if (prc[f]) return mij_fail(prc[f], "decoder_decode: stream %d rejected", f);
-    const Parsed &P = d->parsed[f];
-    if (P.w > d->max_w || P.h > d->max_h)
-      return mij_fail(MIJ_EINVAL, "stream %d: %dx%d exceeds the decoder's %dx%d", f, P.w, P.h, d->max_w, d->max_h);
-  }
-  // slots: raw scan length + >= 16 zero bytes, 8-aligned
-  std::vector<size_t> slot(3 * (size_t)n);
-  size_t off = 0;
-  for (int f = 0; f < n; f++)
-    for (int k = 0; k < 3; k++) {
-      slot[3 * f + k] = off;
-      const auto &sc = d->parsed[f].scan[k];
-      off = (off + (size_t)(sc.end - sc.data) + 16 + 7) & ~(size_t)7;
-    }
-  if (int rc = decoder_stage(d, off)) return rc;
-  std::vector<mij::DecTab> tabs(4 * (size_t)n);
-  std::vector<mij::DecJob> jobs(3 * (size_t)n);
-  const long long fs = d->plane_px * 3 / 2;  // int16 per frame slot
-  parallel([&](int f) {
-    const Parsed &P = d->parsed[f];
-    for (int t = 0; t < 4; t++) tabs[4 * f + t] = P.tab[t];
-    const long long ny = (long long)P.w * P.h;
-    const long long base[3] = {f * fs, f * fs + ny, f * fs + ny + ny / 4};
-    for (int k = 0; k < 3; k++) {
-      const auto &sc = P.scan[k];
-      const size_t at = slot[3 * f + k];
-      const size_t len = unstuff(d->h_blob + at, jpgs[f], (size_t)sc.data, (size_t)sc.end);
-      const size_t next = (at + (size_t)(sc.end - sc.data) + 16 + 7) & ~(size_t)7;
-      memset(d->h_blob + at + len, 0, next - at - len);
-      mij::DecJob &j = jobs[3 * f + k];
-      j.data = (long long)at;
-      j.nbits = 8LL * (long long)len;
-      j.out = base[sc.comp];
-      j.nblocks = (int)(sc.comp ? ny / 256 : ny / 64);
-      j.dc = 4 * f + 2 * sc.td;
-      j.ac = 4 * f + 2 * sc.ta + 1;
-    }
-  });
+// the legacy frames' scans: jobs[3 * i + k] belongs to frame leg[i]
+static int decode_legacy(mij_decoder *d, std::vector<mij::DecJob> &jobs, const std::vector<int> &leg, int *passes_out) {
   int nchunks = 0, max_chunks = 1;
   for (auto &j : jobs) {
     j.chunk0 = nchunks;
-    j.nchunks = std::max(1, (int)((j.nbits + mij::CHUNK - 1) / mij::CHUNK));
     nchunks += j.nchunks;
     max_chunks = std::max(max_chunks, j.nchunks);
   }
-  const int nj = 3 * n;
-  if (int rc = decoder_buffers(d, nchunks, nj)) return rc;
-  HIP_TRY(hipMemcpyAsync(d->d_blob, d->h_blob, off, hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(hipMemcpyAsync(d->d_tabs, tabs.data(), tabs.size() * sizeof(mij::DecTab), hipMemcpyHostToDevice,
-                         d->stream));
+  const int nj = (int)jobs.size();
   HIP_TRY(hipMemcpyAsync(d->d_jobs, jobs.data(), jobs.size() * sizeof(mij::DecJob), hipMemcpyHostToDevice,
                          d->stream));
   HIP_TRY(hipMemsetAsync(d->d_status, 0, nj * sizeof(int), d->stream));
@@ -895,7 +1390,7 @@ extern "C" int mij_decoder_decode(mij_decoder *d, const uint8_t *const *jpgs, co
     HIP_TRY(hipStreamSynchronize(d->stream));
     if (!changed) break;
   }
-  d->last_passes = passes;
+  *passes_out = passes;
   hipLaunchKernelGGL(mij::k_dec_scan, dim3(nj), dim3(256), 0, d->stream, d->d_jobs, d->d_nblk, d->d_base,
                      d->d_status);
   hipLaunchKernelGGL(mij::k_dec_write, grid, dim3(256), 0, d->stream, a, d->d_base, d->d_coef, d->d_status);
@@ -904,7 +1399,240 @@ extern "C" int mij_decoder_decode(mij_decoder *d, const uint8_t *const *jpgs, co
   HIP_TRY(hipMemcpyAsync(st.data(), d->d_status, nj * sizeof(int), hipMemcpyDeviceToHost, d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
   for (int j = 0; j < nj; j++)
-    if (st[j]) return mij_fail(MIJ_EJPEG, "stream %d scan %d: corrupt entropy data (%d)", j / 3, j % 3, st[j]);
+    if (st[j]) return mij_fail(MIJ_EJPEG, "stream %d scan %d: corrupt entropy data (%d)", leg[j / 3], j % 3, st[j]);
+  return MIJ_OK;
+}
+
+// the other frames' restart intervals; their chunk arrays start at chunk `c0`
+// of the decoder's (behind the legacy scans')
+static int decode_interleaved(mij_decoder *d, std::vector<mij::IlJob> &jobs, std::vector<mij::IlFrame> &frames,
+                              const std::vector<int> &fgn, int c0, int *passes_out) {
+  const int nj = (int)jobs.size(), nf = (int)frames.size();
+  int nchunks = 0, max_chunks = 1;
+  for (auto &j : jobs) {
+    mij::IlFrame &F = frames[j.frame];
+    if (F.nchunks == 0) F.chunk0 = nchunks;
+    j.chunk0 = nchunks;
+    nchunks += j.nchunks;
+    F.nchunks += j.nchunks;
+    max_chunks = std::max(max_chunks, j.nchunks);
+  }
+  if (int rc = grow(d->f_jobs, d->f_jobs_cap, (size_t)nj)) return rc;
+  if (int rc = grow(d->f_frames, d->f_frames_cap, (size_t)nf)) return rc;
+  if (int rc = grow(d->f_status, d->f_status_cap, (size_t)nf)) return rc;
+  HIP_TRY(hipMemcpyAsync(d->f_jobs, jobs.data(), nj * sizeof(mij::IlJob), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->f_frames, frames.data(), nf * sizeof(mij::IlFrame), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemsetAsync(d->f_status, 0, nf * sizeof(int), d->stream));
+  mij::IlArgs a{d->d_blob, d->f_jobs, d->f_frames, nj, nchunks, d->d_tabs, d->d_entry + c0, d->d_exit[1] + c0,
+                d->d_exit[0] + c0, d->d_nblk + c0, d->d_changed, 1};
+  const dim3 grid((nchunks + 255) / 256);
+  hipLaunchKernelGGL(mij::k_il_sync, grid, dim3(256), 0, d->stream, a);
+  HIP_TRY(hipGetLastError());
+  int cur = 0, passes = 1;
+  for (;;) {
+    // as above: each pass settles one more chunk of every interval.  The
+    // slot makes interleaved scans settle later than one-component scans (a
+    // chunk may find the right bit and the wrong luma slot, which only the
+    // next chroma block exposes), and a pass in which nothing changes costs
+    // little, so after the first two the host looks only every fourth pass.
+    const int group = passes < 3 ? 1 : 4;
+    if (passes > max_chunks + 1 + group) return mij_fail(MIJ_EJPEG, "decoder: chunk states did not settle");
+    HIP_TRY(hipMemsetAsync(d->d_changed, 0, sizeof(int), d->stream));
+    a.first = 0;
+    for (int g = 0; g < group; g++, passes++) {
+      a.exit_in = d->d_exit[cur] + c0;
+      a.exit_out = d->d_exit[!cur] + c0;
+      hipLaunchKernelGGL(mij::k_il_sync, grid, dim3(256), 0, d->stream, a);
+      cur = !cur;
+    }
+    HIP_TRY(hipGetLastError());
+    int changed = 0;
+    HIP_TRY(hipMemcpyAsync(&changed, d->d_changed, sizeof(int), hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    if (!changed) break;
+  }
+  *passes_out = passes;
+  hipLaunchKernelGGL(mij::k_il_scan, dim3(nf), dim3(256), 0, d->stream, d->f_frames, d->d_nblk + c0, d->d_base + c0);
+  hipLaunchKernelGGL(mij::k_il_write, grid, dim3(256), 0, d->stream, a, d->d_base + c0, d->f_coef, d->f_status);
+  HIP_TRY(hipGetLastError());
+  std::vector<int> st(nf);
+  HIP_TRY(hipMemcpyAsync(st.data(), d->f_status, nf * sizeof(int), hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  for (int j = 0; j < nf; j++)
+    if (st[j]) return mij_fail(MIJ_EJPEG, "stream %d: corrupt entropy data (%d)", fgn[j], st[j]);
+  return MIJ_OK;
+}
+
+// Parses n streams, stages their unstuffed scans and restart intervals in
+// one device blob and decodes them chunk-parallel.  Synchronous; the
+// coefficients stay on the device (mij_decoder_coefs / _component).
+extern "C" int mij_decoder_decode(mij_decoder *d, const uint8_t *const *jpgs, const size_t *lens, int n) {
+  mij_clear_error();
+  if (!d || !jpgs || !lens || n < 1 || n > d->cap) return mij_fail(MIJ_EINVAL, "decoder_decode: bad args");
+  HIP_TRY(hipSetDevice(d->dev));
+  d->n = 0;  // set to n only once every stream decoded cleanly
+  d->rec_valid = false;  // pixels of an earlier decode are no longer served
+  d->parsed.assign(n, Parsed());
+  d->loc.assign(n, FrameLoc());
+  // host work per stream in parallel: parse (finds the scan ends), then
+  // unstuff each piece into its slot (sized by the raw length, an upper bound)
+  const int nth = std::max(1, std::min(n, (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()))));
+  auto parallel = [&](auto &&fn) {
+    std::atomic<int> next{0};
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nth; t++)
+      pool.emplace_back([&] { for (int f; (f = next++) < n;) fn(f); });
+    for (int f; (f = next++) < n;) fn(f);
+    for (auto &th : pool) th.join();
+  };
+  std::vector<int> prc(n, MIJ_OK);
+  for (int f = 0; f < n; f++)
+    if (!jpgs[f]) return mij_fail(MIJ_EINVAL, "decoder_decode: stream %d is NULL", f);
+  parallel([&](int f) { prc[f] = parse(jpgs[f], lens[f], d->parsed[f], f); });
+  std::vector<int> leg, fgn;  // frames of either kind
+  for (int f = 0; f < n; f++) {
+    if (prc[f]) return mij_fail(prc[f], "decoder_decode: %s", d->parsed[f].err);
+    const Parsed &P = d->parsed[f];
+    if (P.w > d->max_w || P.h > d->max_h)
+      return mij_fail(MIJ_EINVAL, "stream %d: %dx%d exceeds the decoder's %dx%d", f, P.w, P.h, d->max_w, d->max_h);
+    (P.legacy ? leg : fgn).push_back(f);
+  }
+  // pieces (a legacy scan, or one restart interval): raw length + >= 16 zero
+  // bytes, 8-aligned
+  struct Piece {
+    size_t at, next;
+    long long data, end;
+    size_t len;
+  };
+  std::vector<Piece> pieces;
+  std::vector<size_t> piece0(n + 1);
+  size_t off = 0;
+  for (int f = 0; f < n; f++) {
+    const Parsed &P = d->parsed[f];
+    piece0[f] = pieces.size();
+    auto add = [&](long long b, long long e) {
+      const size_t next = (off + (size_t)(e - b) + 16 + 7) & ~(size_t)7;
+      pieces.push_back({off, next, b, e, 0});
+      off = next;
+    };
+    if (P.legacy)
+      for (int k = 0; k < 3; k++) add(P.scan[k].data, P.scan[k].end);
+    else
+      for (const auto &iv : P.ivl) add(iv.data, iv.end);
+  }
+  piece0[n] = pieces.size();
+  // chunk ids are ints: every piece has max(1, ceil(bits / 512)) chunks
+  if (off / 64 + pieces.size() > 0x7fff0000u) return mij_fail(MIJ_EINVAL, "decoder_decode: too much entropy data");
+  if (int rc = decoder_stage(d, off)) return rc;
+  // the arena of the frames that are not of the legacy shape
+  const long long fs = d->plane_px * 3 / 2;  // int16 per legacy frame slot
+  long long units = 0, pixb = 0;
+  for (int f = 0; f < n; f++) {
+    const Parsed &P = d->parsed[f];
+    FrameLoc &L = d->loc[f];
+    if (P.legacy) {
+      const long long ny = (long long)P.w * P.h;
+      L.off[0] = f * fs;
+      L.off[1] = f * fs + ny;
+      L.off[2] = f * fs + ny + ny / 4;
+      L.pix = f * d->plane_px * 3;
+    } else {
+      L.foreign = true;
+      for (int c = 0; c < P.ncomp; c++) {
+        L.off[c] = units;
+        units += 64LL * P.bw[c] * P.bh[c];
+      }
+      L.pix = pixb;
+      pixb += P.pitch() * P.h;
+    }
+  }
+  d->f_pix_bytes = pixb;
+  if (int rc = grow(d->f_coef, d->f_coef_cap, (size_t)units)) return rc;
+  std::vector<mij::DecTab> tabs(4 * (size_t)n);
+  parallel([&](int f) {
+    const Parsed &P = d->parsed[f];
+    for (int t = 0; t < 4; t++) tabs[4 * f + t] = P.tab[t];
+    for (size_t p = piece0[f]; p < piece0[f + 1]; p++) {
+      Piece &pc = pieces[p];
+      pc.len = unstuff(d->h_blob + pc.at, jpgs[f], (size_t)pc.data, (size_t)pc.end);
+      memset(d->h_blob + pc.at + pc.len, 0, pc.next - pc.at - pc.len);
+    }
+  });
+  auto chunks_of = [](long long nbits) { return std::max(1, (int)((nbits + mij::CHUNK - 1) / mij::CHUNK)); };
+  std::vector<mij::DecJob> jobs(3 * leg.size());
+  for (size_t i = 0; i < leg.size(); i++) {
+    const int f = leg[i];
+    const Parsed &P = d->parsed[f];
+    const long long ny = (long long)P.w * P.h;
+    for (int k = 0; k < 3; k++) {
+      const auto &sc = P.scan[k];
+      const Piece &pc = pieces[piece0[f] + k];
+      mij::DecJob &j = jobs[3 * i + k];
+      j.data = (long long)pc.at;
+      j.nbits = 8LL * (long long)pc.len;
+      j.out = d->loc[f].off[sc.comp];
+      j.nblocks = (int)(sc.comp ? ny / 256 : ny / 64);
+      j.dc = 4 * f + 2 * sc.td;
+      j.ac = 4 * f + 2 * sc.ta + 1;
+      j.nchunks = chunks_of(j.nbits);
+    }
+  }
+  std::vector<mij::IlFrame> iframes(fgn.size());
+  std::vector<mij::IlJob> ijobs;
+  for (size_t i = 0; i < fgn.size(); i++) {
+    const int f = fgn[i];
+    const Parsed &P = d->parsed[f];
+    mij::IlFrame &F = iframes[i];
+    memset(&F, 0, sizeof F);
+    F.ncomp = P.ncomp;
+    F.mcus_x = P.mcus_x;
+    F.nmcus = P.mcus_x * P.mcus_y;
+    for (int c = 0; c < P.ncomp; c++) {
+      F.off[c] = d->loc[f].off[c];
+      F.hs[c] = P.hs[c];
+      F.vs[c] = P.vs[c];
+      F.bw[c] = P.bw[c];
+      F.dc[c] = 4 * f + 2 * P.td[c];
+      F.ac[c] = 4 * f + 2 * P.ta[c] + 1;
+      for (int y = 0; y < P.vs[c]; y++)
+        for (int x = 0; x < P.hs[c]; x++) {  // at most 2 * 2 + 1 + 1 = 6: parse() admits no other sampling
+          F.slot_comp[F.bpm] = c;
+          F.slot_x[F.bpm] = x;
+          F.slot_y[F.bpm] = y;
+          F.bpm++;
+        }
+    }
+    const int ri = P.ri ? P.ri : F.nmcus;
+    for (size_t k = 0; k < P.ivl.size(); k++) {
+      const Piece &pc = pieces[piece0[f] + k];
+      mij::IlJob j;
+      j.data = (long long)pc.at;
+      j.nbits = 8LL * (long long)pc.len;
+      j.frame = (int)i;
+      // parse() made the interval count ceil(nmcus / ri), so mcu0 < nmcus and
+      // mcu0 + nmcus_i <= nmcus: what bounds k_il_write's stores
+      j.mcu0 = (int)((long long)k * ri);
+      j.nmcus = std::min(ri, F.nmcus - j.mcu0);
+      j.chunk0 = 0;
+      j.nchunks = chunks_of(j.nbits);
+      j.pad = 0;
+      if (j.mcu0 >= F.nmcus || j.nmcus < 1) return mij_fail(MIJ_EJPEG, "stream %d: restart interval %zu has no MCUs", f, k);
+      ijobs.push_back(j);
+    }
+  }
+  long long nch_leg = 0, nch_il = 0;
+  for (auto &j : jobs) nch_leg += j.nchunks;
+  for (auto &j : ijobs) nch_il += j.nchunks;
+  if (int rc = decoder_buffers(d, (int)(nch_leg + nch_il), 0)) return rc;
+  HIP_TRY(hipMemcpyAsync(d->d_blob, d->h_blob, off, hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->d_tabs, tabs.data(), tabs.size() * sizeof(mij::DecTab), hipMemcpyHostToDevice,
+                         d->stream));
+  int p1 = 0, p2 = 0;
+  if (!leg.empty())
+    if (int rc = decode_legacy(d, jobs, leg, &p1)) return rc;
+  if (!fgn.empty())
+    if (int rc = decode_interleaved(d, ijobs, iframes, fgn, (int)nch_leg, &p2)) return rc;
+  d->last_passes = std::max(p1, p2);
   d->n = n;
   return MIJ_OK;
 }
@@ -917,9 +1645,24 @@ extern "C" int mij_decoder_info(mij_decoder *d, int frame, int *w, int *h, uint8
   const Parsed &P = d->parsed[frame];
   if (w) *w = P.w;
   if (h) *h = P.h;
-  if (dqt) {
-    memcpy(dqt, P.dqt[0], 64);
-    memcpy(dqt + 64, P.dqt[1], 64);
+  if (dqt) {  // the tables of components 0 and 1 (greyscale: component 0 twice)
+    memcpy(dqt, P.dqt[P.tq[0]], 64);
+    memcpy(dqt + 64, P.dqt[P.tq[P.ncomp > 1 ? 1 : 0]], 64);
+  }
+  return MIJ_OK;
+}
+
+extern "C" int mij_decoder_layout(mij_decoder *d, int frame, int *out, int n) {
+  mij_clear_error();
+  if (!d || frame < 0 || frame >= d->n || !out) return mij_fail(MIJ_EINVAL, "decoder_layout: bad args");
+  const Parsed &P = d->parsed[frame];
+  const int need = 9 + 5 * P.ncomp;
+  if (n < need) return mij_fail(MIJ_ENOSPC, "decoder_layout: need %d ints", need);
+  const int head[9] = {P.w, P.h, P.ncomp, P.hmax, P.vmax, P.mcus_x, P.mcus_y, P.ri, P.interleaved ? 1 : 0};
+  memcpy(out, head, sizeof head);
+  for (int c = 0; c < P.ncomp; c++) {
+    const int e[5] = {P.hs[c], P.vs[c], P.tq[c], P.bw[c], P.bh[c]};
+    memcpy(out + 9 + 5 * c, e, sizeof e);
   }
   return MIJ_OK;
 }
@@ -927,6 +1670,9 @@ extern "C" int mij_decoder_info(mij_decoder *d, int frame, int *w, int *h, uint8
 extern "C" int mij_decoder_coefs(mij_decoder *d, int frame, int16_t *Y, int16_t *Cb, int16_t *Cr) {
   mij_clear_error();
   if (!d || frame < 0 || frame >= d->n || !Y || !Cb || !Cr) return mij_fail(MIJ_EINVAL, "decoder_coefs: bad args");
+  if (d->loc[frame].foreign)
+    return mij_fail(MIJ_EINVAL, "decoder_coefs: frame %d is not of the encoder's layout; use mij_decoder_layout and "
+                    "mij_decoder_component", frame);
   HIP_TRY(hipSetDevice(d->dev));
   const Parsed &P = d->parsed[frame];
   const long long ny = (long long)P.w * P.h;
@@ -938,16 +1684,51 @@ extern "C" int mij_decoder_coefs(mij_decoder *d, int frame, int16_t *Y, int16_t 
   return MIJ_OK;
 }
 
+// A component's padded plane as jpeg_read_coefficients shows it: the device
+// holds the coded DC differences (the IDCT takes its absolute DCs from the
+// prefix sums of reconstruct), so the prediction is undone here on the host,
+// in scan order and from 0 at every restart interval.
+extern "C" int mij_decoder_component(mij_decoder *d, int frame, int comp, int16_t *dst, size_t cap) {
+  mij_clear_error();
+  if (!d || frame < 0 || frame >= d->n || !dst) return mij_fail(MIJ_EINVAL, "decoder_component: bad args");
+  const Parsed &P = d->parsed[frame];
+  if (comp < 0 || comp >= P.ncomp) return mij_fail(MIJ_EINVAL, "decoder_component: component %d of %d", comp, P.ncomp);
+  const long long nb = (long long)P.bw[comp] * P.bh[comp];
+  if (cap < (size_t)(64 * nb)) return mij_fail(MIJ_ENOSPC, "decoder_component: need %lld coefficients", 64 * nb);
+  HIP_TRY(hipSetDevice(d->dev));
+  const FrameLoc &L = d->loc[frame];
+  const int16_t *src = (L.foreign ? d->f_coef : d->d_coef) + L.off[comp];
+  HIP_TRY(hipMemcpyAsync(dst, src, (size_t)(128 * nb), hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  // legacy: a one-component scan predicts in raster order, never resets
+  const int hs = L.foreign ? P.hs[comp] : 1, vs = L.foreign ? P.vs[comp] : 1;
+  const int mx_n = P.bw[comp] / hs;
+  const long long seg = L.foreign && P.ri ? (long long)P.ri * hs * vs : nb;
+  uint32_t run = 0;
+  for (long long s = 0; s < nb; s++) {
+    const long long m = s / (hs * vs), i = s % (hs * vs);
+    const long long my = m / mx_n, mx = m % mx_n;
+    const long long r = (my * vs + i / hs) * P.bw[comp] + mx * hs + i % hs;
+    if (s % seg == 0) run = 0;
+    run += (uint32_t)(int32_t)dst[64 * r];
+    dst[64 * r] = (int16_t)run;
+  }
+  return MIJ_OK;
+}
+
 extern "C" void *mij_decoder_device_coefs(mij_decoder *d, int frame) {
   if (!d || frame < 0 || frame >= d->n) return nullptr;
-  return d->d_coef + frame * (d->plane_px * 3 / 2);
+  const FrameLoc &L = d->loc[frame];
+  return (L.foreign ? d->f_coef : d->d_coef) + L.off[0];
 }
 
 // ---------------------------------------------------------------------------
 // pixels: host side
 // ---------------------------------------------------------------------------
-static int decoder_rec_buffers(mij_decoder *d) {
-  if (d->rec_ready) return MIJ_OK;
+static int decoder_rec_buffers(mij_decoder *d, bool legacy) {
+  for (hipEvent_t &e : d->rec_ev)
+    if (!e) HIP_TRY(hipEventCreate(&e));
+  if (d->rec_ready || !legacy) return MIJ_OK;
   const size_t fs = (size_t)d->plane_px * 3 / 2, cap = (size_t)d->cap;
   auto alloc = [&]() -> int {
     HIP_TRY(hipMalloc((void **)&d->d_planes, cap * fs));
@@ -958,7 +1739,6 @@ static int decoder_rec_buffers(mij_decoder *d) {
     HIP_TRY(hipMalloc((void **)&d->d_tile, cap * (fs / 64 / mij::DC_TILE + 3) * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void **)&d->d_rjobs, cap * 3 * sizeof(mij::RecJob)));
     HIP_TRY(hipMalloc((void **)&d->d_rframes, cap * sizeof(mij::RecFrame)));
-    for (hipEvent_t &e : d->rec_ev) HIP_TRY(hipEventCreate(&e));
     return MIJ_OK;
   };
   if (int rc = alloc()) {  // all or nothing: the next call starts over
@@ -967,14 +1747,18 @@ static int decoder_rec_buffers(mij_decoder *d) {
       hipFree(*p);
       *p = nullptr;
     }
-    for (hipEvent_t &e : d->rec_ev) {
-      if (e) hipEventDestroy(e);
-      e = nullptr;
-    }
     return rc;
   }
   d->rec_ready = true;
   return MIJ_OK;
+}
+
+static int pix_mode(const Parsed &P) {
+  if (P.ncomp == 1) return mij::PIX_GREY;
+  if (P.hmax == 1) return mij::PIX_444;
+  const bool rep = (P.w + 1) / 2 <= 2;  // libjpeg: fancy only for downsampled_width > 2
+  if (P.vmax == 1) return rep ? mij::PIX_H2V1_REP : mij::PIX_H2V1;
+  return rep ? mij::PIX_H2V2_REP : mij::PIX_H2V2;
 }
 
 extern "C" int mij_decoder_reconstruct(mij_decoder *d, int order) {
@@ -984,26 +1768,28 @@ extern "C" int mij_decoder_reconstruct(mij_decoder *d, int order) {
     return mij_fail(MIJ_EINVAL, "decoder_reconstruct: pixel order %d", order);
   if (d->n < 1) return mij_fail(MIJ_EINVAL, "decoder_reconstruct: no decoded frames");
   HIP_TRY(hipSetDevice(d->dev));
-  if (int rc = decoder_rec_buffers(d)) return rc;
+  const int n = d->n;
+  int nl = 0, nf = 0;
+  for (int f = 0; f < n; f++) (d->loc[f].foreign ? nf : nl)++;
+  if (int rc = decoder_rec_buffers(d, nl > 0)) return rc;
   // the previous call's uploads read these vectors: let them finish first
   HIP_TRY(hipStreamSynchronize(d->stream));
   d->rec_valid = false;
-  const int n = d->n;
-  const long long fs = d->plane_px * 3 / 2;
-  d->h_rjobs.resize(3 * (size_t)n);
-  d->h_rframes.resize(n);
+  d->h_rjobs.resize(3 * (size_t)nl);
+  d->h_rframes.resize(nl);
   d->h_recq.resize(128 * (size_t)n);
   long long idct_wgs = 0, col_wgs = 0, tiles = 0;
+  int li = 0;
   for (int f = 0; f < n; f++) {
     const Parsed &P = d->parsed[f];
-    if (!P.have_dqt[0] || !P.have_dqt[1]) return mij_fail(MIJ_EJPEG, "stream %d: DQT missing", f);
+    if (d->loc[f].foreign) continue;
+    if (!P.have_dqt[P.tq[0]] || !P.have_dqt[P.tq[1]]) return mij_fail(MIJ_EJPEG, "stream %d: DQT missing", f);
     for (int t = 0; t < 2; t++)
-      for (int z = 0; z < 64; z++) d->h_recq[128 * f + 64 * t + z] = P.dqt[t][z];
+      for (int z = 0; z < 64; z++) d->h_recq[128 * f + 64 * t + z] = P.dqt[P.tq[t]][z];
     const long long ny = (long long)P.w * P.h;
-    const long long off[3] = {f * fs, f * fs + ny, f * fs + ny + ny / 4};
     for (int c = 0; c < 3; c++) {
-      mij::RecJob &j = d->h_rjobs[3 * f + c];
-      j.off = off[c];
+      mij::RecJob &j = d->h_rjobs[3 * li + c];
+      j.off = d->loc[f].off[c];
       j.nblocks = (int)(c ? ny / 256 : ny / 64);
       j.bw = c ? P.w / 16 : P.w / 8;
       j.wg0 = (int)idct_wgs;
@@ -1013,33 +1799,115 @@ extern "C" int mij_decoder_reconstruct(mij_decoder *d, int order) {
       idct_wgs += (j.nblocks + 255) / 256;
       tiles += (j.nblocks + mij::DC_TILE - 1) / mij::DC_TILE;
     }
-    mij::RecFrame &fr = d->h_rframes[f];
-    fr.planes = f * fs;
-    fr.pix = f * d->plane_px * 3;
+    mij::RecFrame &fr = d->h_rframes[li++];
+    fr.planes = d->loc[f].off[0];
+    fr.pix = d->loc[f].pix;
     fr.w = P.w;
     fr.h = P.h;
     fr.wg0 = (int)col_wgs;
     fr.pad = 0;
     col_wgs += ((long long)(P.h / 2) * (P.w / 16) + 255) / 256;
   }
-  if (idct_wgs > 0x7fffffff || col_wgs > 0x7fffffff) return mij_fail(MIJ_EINVAL, "decoder_reconstruct: too many blocks");
-  HIP_TRY(hipMemcpyAsync(d->d_rjobs, d->h_rjobs.data(), d->h_rjobs.size() * sizeof(mij::RecJob),
-                         hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(hipMemcpyAsync(d->d_rframes, d->h_rframes.data(), d->h_rframes.size() * sizeof(mij::RecFrame),
-                         hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(hipMemcpyAsync(d->d_recq, d->h_recq.data(), d->h_recq.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                         d->stream));
+  // the frames in the arena: one IlRec per component, one IlPix per frame
+  d->h_irec.clear();
+  d->h_ipix.clear();
+  d->h_irecq.clear();
+  long long i_wgs = 0, i_col = 0, i_tiles = 0, units = 0;
+  for (int f = 0; f < n; f++) {
+    const Parsed &P = d->parsed[f];
+    const FrameLoc &L = d->loc[f];
+    if (!L.foreign) continue;
+    for (int c = 0; c < P.ncomp; c++) {
+      mij::IlRec j;
+      j.off = L.off[c];
+      j.nblocks = P.bw[c] * P.bh[c];
+      j.bw = P.bw[c];
+      j.wg0 = (int)i_wgs;
+      j.qt = (int)(d->h_irecq.size() / 64);
+      j.tile0 = (int)i_tiles;
+      j.hs = P.hs[c];
+      j.vs = P.vs[c];
+      j.mcus_x = P.mcus_x;
+      j.seg = P.ri ? (int)std::min<long long>((long long)P.ri * P.hs[c] * P.vs[c], j.nblocks) : j.nblocks;
+      j.pad = 0;
+      for (int z = 0; z < 64; z++) d->h_irecq.push_back(P.dqt[P.tq[c]][z]);
+      i_wgs += (j.nblocks + 255) / 256;
+      i_tiles += (j.nblocks + mij::DC_TILE - 1) / mij::DC_TILE;
+      units = std::max(units, j.off + 64LL * j.nblocks);
+      d->h_irec.push_back(j);
+    }
+    mij::IlPix px;
+    memset(&px, 0, sizeof px);
+    px.y = L.off[0];
+    px.cb = L.off[P.ncomp > 1 ? 1 : 0];
+    px.cr = L.off[P.ncomp > 1 ? 2 : 0];
+    px.pix = L.pix;
+    px.G.w = P.w;
+    px.G.h = P.h;
+    px.G.mode = pix_mode(P);
+    px.G.yp = 8 * P.bw[0];
+    px.G.cp = P.ncomp > 1 ? 8 * P.bw[1] : 8 * P.bw[0];
+    px.G.cw = (P.w + P.hmax - 1) / P.hmax;
+    px.G.ch = (P.h + P.vmax - 1) / P.vmax;
+    px.G.pitch = P.pitch();
+    px.groups = (P.w + 15) / 16;
+    const int rows = mij::pix_rows_per_lane(px.G.mode);
+    px.units = (P.h + rows - 1) / rows;
+    px.wg0 = (int)i_col;
+    i_col += ((long long)px.units * px.groups + 255) / 256;
+    d->h_ipix.push_back(px);
+  }
+  if (idct_wgs > 0x7fffffff || col_wgs > 0x7fffffff || i_wgs > 0x7fffffff || i_col > 0x7fffffff)
+    return mij_fail(MIJ_EINVAL, "decoder_reconstruct: too many blocks");
+  if (nf) {
+    if (int rc = grow(d->f_planes, d->f_planes_cap, (size_t)units)) return rc;
+    if (int rc = grow(d->f_dc, d->f_dc_cap, (size_t)(units / 64))) return rc;
+    if (int rc = grow(d->f_tile, d->f_tile_cap, (size_t)i_tiles)) return rc;
+    if (int rc = grow(d->f_pix, d->f_pix_cap, (size_t)d->f_pix_bytes)) return rc;
+    if (int rc = grow(d->f_recq, d->f_recq_cap, d->h_irecq.size())) return rc;
+    if (int rc = grow(d->f_rjobs, d->f_rjobs_cap, d->h_irec.size())) return rc;
+    if (int rc = grow(d->f_rpix, d->f_rpix_cap, d->h_ipix.size())) return rc;
+    HIP_TRY(hipMemcpyAsync(d->f_rjobs, d->h_irec.data(), d->h_irec.size() * sizeof(mij::IlRec), hipMemcpyHostToDevice,
+                           d->stream));
+    HIP_TRY(hipMemcpyAsync(d->f_rpix, d->h_ipix.data(), d->h_ipix.size() * sizeof(mij::IlPix), hipMemcpyHostToDevice,
+                           d->stream));
+    HIP_TRY(hipMemcpyAsync(d->f_recq, d->h_irecq.data(), d->h_irecq.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                           d->stream));
+  }
+  if (nl) {
+    HIP_TRY(hipMemcpyAsync(d->d_rjobs, d->h_rjobs.data(), d->h_rjobs.size() * sizeof(mij::RecJob),
+                           hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(hipMemcpyAsync(d->d_rframes, d->h_rframes.data(), d->h_rframes.size() * sizeof(mij::RecFrame),
+                           hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(hipMemcpyAsync(d->d_recq, d->h_recq.data(), d->h_recq.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                           d->stream));
+  }
   HIP_TRY(hipEventRecord(d->rec_ev[0], d->stream));
-  hipLaunchKernelGGL(mij::k_dec_dc, dim3((unsigned)tiles), dim3(mij::DC_T), 0, d->stream, d->d_rjobs, 3 * n,
-                     d->d_coef, d->d_dc, d->d_tile);
-  hipLaunchKernelGGL(mij::k_dec_dcbase, dim3((3 * n + 63) / 64), dim3(64), 0, d->stream, d->d_rjobs, 3 * n,
-                     d->d_tile);
-  hipLaunchKernelGGL(mij::k_dec_idct, dim3((unsigned)idct_wgs), dim3(256), 0, d->stream, d->d_rjobs, 3 * n,
-                     d->d_coef, d->d_dc, d->d_tile, d->d_recq, d->d_planes);
+  if (nl) {
+    hipLaunchKernelGGL(mij::k_dec_dc, dim3((unsigned)tiles), dim3(mij::DC_T), 0, d->stream, d->d_rjobs, 3 * nl,
+                       d->d_coef, d->d_dc, d->d_tile);
+    hipLaunchKernelGGL(mij::k_dec_dcbase<mij::RecJob>, dim3((3 * nl + 63) / 64), dim3(64), 0, d->stream, d->d_rjobs,
+                       3 * nl, d->d_tile);
+    hipLaunchKernelGGL(mij::k_dec_idct, dim3((unsigned)idct_wgs), dim3(256), 0, d->stream, d->d_rjobs, 3 * nl,
+                       d->d_coef, d->d_dc, d->d_tile, d->d_recq, d->d_planes);
+  }
+  const int nir = (int)d->h_irec.size();
+  if (nf) {
+    hipLaunchKernelGGL(mij::k_il_dc, dim3((unsigned)i_tiles), dim3(mij::DC_T), 0, d->stream, d->f_rjobs, nir,
+                       d->f_coef, d->f_dc, d->f_tile);
+    hipLaunchKernelGGL(mij::k_dec_dcbase<mij::IlRec>, dim3((nir + 63) / 64), dim3(64), 0, d->stream, d->f_rjobs, nir,
+                       d->f_tile);
+    hipLaunchKernelGGL(mij::k_il_idct, dim3((unsigned)i_wgs), dim3(256), 0, d->stream, d->f_rjobs, nir, d->f_coef,
+                       d->f_dc, d->f_tile, d->f_recq, d->f_planes);
+  }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(d->rec_ev[1], d->stream));
-  hipLaunchKernelGGL(mij::k_dec_colour, dim3((unsigned)col_wgs), dim3(256), 0, d->stream, d->d_rframes, n,
-                     d->d_planes, d->d_pix, order == MIJ_PIX_RGB);
+  if (nl)
+    hipLaunchKernelGGL(mij::k_dec_colour, dim3((unsigned)col_wgs), dim3(256), 0, d->stream, d->d_rframes, nl,
+                       d->d_planes, d->d_pix, order == MIJ_PIX_RGB);
+  if (nf)
+    hipLaunchKernelGGL(mij::k_il_colour, dim3((unsigned)i_col), dim3(256), 0, d->stream, d->f_rpix, nf, d->f_planes,
+                       d->f_pix, order == MIJ_PIX_RGB);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(d->rec_ev[2], d->stream));
   d->rec_valid = true;
@@ -1066,7 +1934,9 @@ extern "C" int mij_decoder_pixels(mij_decoder *d, int frame, uint8_t *dst, size_
   const unsigned long long need = (unsigned long long)(P->h - 1) * pitch + row;
   if (cap < need) return mij_fail(MIJ_ENOSPC, "decoder_pixels: need %llu bytes", need);
   HIP_TRY(hipSetDevice(d->dev));
-  HIP_TRY(hipMemcpy2DAsync(dst, (size_t)pitch, d->d_pix + frame * d->plane_px * 3, (size_t)row, (size_t)row, P->h,
+  const FrameLoc &L = d->loc[frame];
+  const uint8_t *src = (L.foreign ? d->f_pix : d->d_pix) + L.pix;
+  HIP_TRY(hipMemcpy2DAsync(dst, (size_t)pitch, src, (size_t)(L.foreign ? P->pitch() : row), (size_t)row, P->h,
                            hipMemcpyDeviceToHost, d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
   return MIJ_OK;
@@ -1077,6 +1947,9 @@ extern "C" int mij_decoder_planes(mij_decoder *d, int frame, uint8_t *Y, uint8_t
   const Parsed *P;
   if (int rc = rec_frame(d, frame, "decoder_planes", &P)) return rc;
   if (!Y || !Cb || !Cr) return mij_fail(MIJ_EINVAL, "decoder_planes: NULL plane");
+  if (d->loc[frame].foreign)
+    return mij_fail(MIJ_EINVAL, "decoder_planes: frame %d is not of the encoder's layout; use mij_decoder_layout and "
+                    "mij_decoder_plane", frame);
   HIP_TRY(hipSetDevice(d->dev));
   const long long ny = (long long)P->w * P->h;
   const uint8_t *src = d->d_planes + frame * (d->plane_px * 3 / 2);
@@ -1087,12 +1960,29 @@ extern "C" int mij_decoder_planes(mij_decoder *d, int frame, uint8_t *Y, uint8_t
   return MIJ_OK;
 }
 
+extern "C" int mij_decoder_plane(mij_decoder *d, int frame, int comp, uint8_t *dst, size_t cap) {
+  mij_clear_error();
+  const Parsed *P;
+  if (int rc = rec_frame(d, frame, "decoder_plane", &P)) return rc;
+  if (!dst) return mij_fail(MIJ_EINVAL, "decoder_plane: dst is NULL");
+  if (comp < 0 || comp >= P->ncomp) return mij_fail(MIJ_EINVAL, "decoder_plane: component %d of %d", comp, P->ncomp);
+  const size_t nbytes = (size_t)64 * P->bw[comp] * P->bh[comp];
+  if (cap < nbytes) return mij_fail(MIJ_ENOSPC, "decoder_plane: need %zu bytes", nbytes);
+  HIP_TRY(hipSetDevice(d->dev));
+  const FrameLoc &L = d->loc[frame];
+  HIP_TRY(hipMemcpyAsync(dst, (L.foreign ? d->f_planes : d->d_planes) + L.off[comp], nbytes, hipMemcpyDeviceToHost,
+                         d->stream));
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  return MIJ_OK;
+}
+
 extern "C" void *mij_decoder_device_pixels(mij_decoder *d, int frame, long long *pitch) {
   mij_clear_error();
   const Parsed *P;
   if (rec_frame(d, frame, "decoder_device_pixels", &P)) return nullptr;
-  if (pitch) *pitch = 3LL * P->w;
-  return d->d_pix + frame * d->plane_px * 3;
+  const FrameLoc &L = d->loc[frame];
+  if (pitch) *pitch = L.foreign ? P->pitch() : 3LL * P->w;  // legacy widths: 3 * w is a multiple of 16 already
+  return (L.foreign ? d->f_pix : d->d_pix) + L.pix;
 }
 
 extern "C" int mij_decoder_reconstruct_ms(mij_decoder *d, float ms[2]) {
@@ -1113,12 +2003,12 @@ extern "C" int mij_decode(const uint8_t *jpg, size_t len, int order, uint8_t *ou
   if (!jpg || !out) return mij_fail(MIJ_EINVAL, "mij_decode: NULL buffer");
   if (order != MIJ_PIX_BGR && order != MIJ_PIX_RGB) return mij_fail(MIJ_EINVAL, "mij_decode: pixel order %d", order);
   Parsed P;  // the size first: the decoder is made for it
-  if (int rc = parse(jpg, len, P, 0)) return rc;
+  if (int rc = parse(jpg, len, P, 0)) return mij_fail(rc, "mij_decode: %s", P.err);
   if (w) *w = P.w;
   if (h) *h = P.h;
   const unsigned long long need = 3ULL * P.w * P.h;
   if (cap < need) return mij_fail(MIJ_ENOSPC, "mij_decode: need %llu bytes", need);
-  mij_decoder *d = mij_decoder_create(mij_drop_device(), P.w, P.h, 1);
+  mij_decoder *d = mij_decoder_create(mij_drop_device(), (P.w + 15) / 16 * 16, (P.h + 15) / 16 * 16, 1);
   if (!d) return mij_last_error();
   int rc = mij_decoder_decode(d, &jpg, &len, 1);
   if (!rc) rc = mij_decoder_reconstruct(d, order);

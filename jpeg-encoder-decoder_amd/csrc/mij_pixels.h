@@ -192,4 +192,137 @@ MIJ_HD void colour_tile(const uint8_t *Y, const uint8_t *Cb, const uint8_t *Cr, 
   }
 }
 
+// ---------------------------------------------------------------------------
+// Every other layout the decoder accepts (DESIGN.md "Decoding ordinary
+// baseline files"): greyscale, 4:4:4, 4:2:2 and 4:2:0 at any size, on planes
+// padded to whole MCUs.  libjpeg's rules: the chroma edges are those of the
+// component's real size, ceil(w / 2) x ceil(h / 2) (downsampled_width /
+// _height), not of the padded plane; the "fancy" upsamplers only run when
+// that width is > 2, else each sample is replicated (jdsample.c).
+// ---------------------------------------------------------------------------
+enum { PIX_GREY = 0, PIX_444 = 1, PIX_H2V1 = 2, PIX_H2V1_REP = 3, PIX_H2V2 = 4, PIX_H2V2_REP = 5 };
+
+struct PixGeom {
+  int w, h;         // the frame's real size
+  int mode;         // PIX_*
+  int yp, cp;       // bytes between rows of the padded luma / chroma planes (multiples of 8)
+  int cw, ch;       // the chroma planes' real size
+  long long pitch;  // bytes between pixel rows: 3 * w rounded up to 16
+};
+
+MIJ_HD int pix_rows_per_lane(int mode) { return mode >= PIX_H2V2 ? 2 : 1; }
+
+// 16 samples at columns x0 .. x0 + 15 (x0 % 16 == 0) of a padded row whose
+// length is a multiple of 8: the second 8 may lie past it (then never shown)
+MIJ_HD void row16(const uint8_t *row, int x0, int rowlen, uint32_t wd[4]) {
+  const W2 a = load_as<W2>(row + x0);
+  W2 b = {0, 0};
+  if (x0 + 8 < rowlen) b = load_as<W2>(row + x0 + 8);
+  wd[0] = a.x;
+  wd[1] = a.y;
+  wd[2] = b.x;
+  wd[3] = b.y;
+}
+
+// chroma10 on a padded row of real width cw: columns past cw - 1 replicate it
+MIJ_HD void chroma10_edge(const uint8_t *row, int c0, int cw, int v[10]) {
+  const int cl = c0 > 0 ? c0 - 1 : 0, cr = c0 + 8 < cw ? c0 + 8 : cw - 1;
+  chroma10(row, c0, cl, cr, v);
+  if (c0 + 8 > cw) {
+    const int last = row[cw - 1];
+  MIJ_UNROLL
+    for (int k = 1; k < 9; k++)
+      if (c0 - 1 + k >= cw) v[k] = last;
+  }
+}
+
+// jdsample.c h2v1_fancy_upsample: p = chroma samples c0-1 .. c0+8
+MIJ_HD void upsample16_h2v1(const int p[10], int out[16]) {
+  MIJ_UNROLL
+  for (int k = 0; k < 8; k++) {
+    out[2 * k] = (3 * p[k + 1] + p[k] + 1) >> 2;
+    out[2 * k + 1] = (3 * p[k + 1] + p[k + 2] + 2) >> 2;
+  }
+}
+
+MIJ_HD void replicate16(const int p[10], int out[16]) {
+  MIJ_UNROLL
+  for (int k = 0; k < 8; k++) out[2 * k] = out[2 * k + 1] = p[k + 1];
+}
+
+// up to three aligned 16-byte stores of one output row's 16-pixel group; the
+// row is G.pitch bytes long (a multiple of 16), so a store that begins inside
+// it ends inside it.  Bytes between 3 * w and the pitch receive anything.
+MIJ_HD void store_group(uint8_t *rowp, int g, long long pitch, const uint32_t wd[12]) {
+  MIJ_UNROLL
+  for (int j = 0; j < 3; j++)
+    if (48LL * g + 16 * j < pitch) store_as(rowp + 48LL * g + 16 * j, W4{wd[4 * j], wd[4 * j + 1], wd[4 * j + 2], wd[4 * j + 3]});
+}
+
+// Unit u, group g: output columns 16g .. 16g+15 of row u (one-row modes) or of
+// rows 2u and 2u+1 (h2v2 modes; the second only if < h).  g < ceil(w / 16),
+// u < h or ceil(h / 2).  Reads stay inside the padded planes (their rows are
+// yp / cp long and there are at least h, resp. ch, of them); stores stay
+// inside rows < h of the frame's pixel slot.
+MIJ_HD void colour_tile_any(const uint8_t *Y, const uint8_t *Cb, const uint8_t *Cr, const PixGeom &G, int u, int g,
+                            int rgb, uint8_t *pix) {
+  const int nrows = pix_rows_per_lane(G.mode);
+  int cb[2][16], crv[2][16];
+  if (G.mode == PIX_444) {
+    uint32_t a[4], b[4];
+    row16(Cb + (long long)u * G.cp, 16 * g, G.cp, a);
+    row16(Cr + (long long)u * G.cp, 16 * g, G.cp, b);
+  MIJ_UNROLL
+    for (int p = 0; p < 16; p++) {
+      cb[0][p] = (int)((a[p >> 2] >> (8 * (p & 3))) & 255);
+      crv[0][p] = (int)((b[p >> 2] >> (8 * (p & 3))) & 255);
+    }
+  } else if (G.mode == PIX_H2V2) {
+    const int ru = u > 0 ? u - 1 : 0, rd = u + 1 < G.ch ? u + 1 : G.ch - 1;
+    int mid[10], nb[10];
+    chroma10_edge(Cb + (long long)u * G.cp, 8 * g, G.cw, mid);
+    chroma10_edge(Cb + (long long)ru * G.cp, 8 * g, G.cw, nb);
+    upsample16(mid, nb, cb[0]);
+    chroma10_edge(Cb + (long long)rd * G.cp, 8 * g, G.cw, nb);
+    upsample16(mid, nb, cb[1]);
+    chroma10_edge(Cr + (long long)u * G.cp, 8 * g, G.cw, mid);
+    chroma10_edge(Cr + (long long)ru * G.cp, 8 * g, G.cw, nb);
+    upsample16(mid, nb, crv[0]);
+    chroma10_edge(Cr + (long long)rd * G.cp, 8 * g, G.cw, nb);
+    upsample16(mid, nb, crv[1]);
+  } else if (G.mode != PIX_GREY) {
+    int p[10];
+    chroma10_edge(Cb + (long long)u * G.cp, 8 * g, G.cw, p);
+    if (G.mode == PIX_H2V1) upsample16_h2v1(p, cb[0]);
+    else replicate16(p, cb[0]);
+    chroma10_edge(Cr + (long long)u * G.cp, 8 * g, G.cw, p);
+    if (G.mode == PIX_H2V1) upsample16_h2v1(p, crv[0]);
+    else replicate16(p, crv[0]);
+  MIJ_UNROLL
+    for (int k = 0; k < 16; k++) {
+      cb[1][k] = cb[0][k];
+      crv[1][k] = crv[0][k];
+    }
+  }
+  for (int row = 0; row < nrows; row++) {
+    const long long y = (long long)nrows * u + row;
+    if (y >= G.h) break;
+    uint32_t yw[4], wd[12];
+    row16(Y + y * G.yp, 16 * g, G.yp, yw);
+    if (G.mode == PIX_GREY) {
+  MIJ_UNROLL
+      for (int k = 0; k < 12; k++) wd[k] = 0;
+  MIJ_UNROLL
+      for (int p = 0; p < 16; p++) {
+        const uint32_t v = (yw[p >> 2] >> (8 * (p & 3))) & 255;
+  MIJ_UNROLL
+        for (int k = 0; k < 3; k++) wd[(3 * p + k) >> 2] |= v << (8 * ((3 * p + k) & 3));
+      }
+    } else {
+      colour16(yw, cb[row], crv[row], rgb, wd);
+    }
+    store_group(pix + y * G.pitch, g, G.pitch, wd);
+  }
+}
+
 }  // namespace mij

@@ -1,10 +1,12 @@
 /*
  * decode_jpg.c -- C host for libmijpeg.so's decoder, next to encode_ppm.c.
  *
- * Turns a baseline JPEG of the shape the encoder writes (8-bit, 4:2:0, three
- * one-component scans, width and height multiples of 16) into a P6 PPM
- * through mij_decode: entropy decoding, IDCT, chroma upsampling and colour
- * conversion all run on the GPU.
+ * Turns a baseline JPEG (8-bit; greyscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0; any
+ * size; one interleaved scan with or without restart intervals, as libjpeg,
+ * cameras and browsers write it, or the encoder's own three scans) into a P6
+ * PPM through mij_decode: entropy decoding, IDCT, chroma upsampling and
+ * colour conversion all run on the GPU.  Anything else is refused with the
+ * reason.
  *
  *   decode_jpg <in.jpg> <out.ppm>
  */

@@ -38,6 +38,7 @@ EXPORTS = [
     "mij_decoder_coefs", "mij_decoder_device_coefs", "mij_decoder_passes",
     "mij_decoder_reconstruct", "mij_decoder_pixels", "mij_decoder_planes", "mij_decoder_device_pixels",
     "mij_decoder_reconstruct_ms", "mij_decoder_stream", "mij_decode",
+    "mij_decoder_layout", "mij_decoder_component", "mij_decoder_plane",
     "mij_detector_create", "mij_detector_destroy", "mij_detector_subsample", "mij_detector_compare",
     "mij_detector_step", "mij_detector_launch", "mij_detector_store", "mij_detector_upload", "mij_detector_get_plane",
     "mij_detector_set_plane", "mij_detector_mask", "mij_detector_stream",
@@ -226,6 +227,9 @@ def load() -> C.CDLL:
         lib.mij_batch_gather_regions.argtypes = [p, p, C.c_longlong, i, i, p, i]
         lib.mij_batch_upload_regions.argtypes = [p, p, i, i, p, i]
         lib.mij_encode_regions.argtypes = [p, i, i, p, i, i, p, sz, p]
+        lib.mij_decoder_layout.argtypes = [p, i, p, i]
+        lib.mij_decoder_component.argtypes = [p, i, i, p, sz]
+        lib.mij_decoder_plane.argtypes = [p, i, i, p, sz]
     except AttributeError:
         if not os.environ.get("MIJ_LIB"):  # older builds only in A/B timing runs
             raise
@@ -895,9 +899,10 @@ def decode(jpg: bytes, order: str = "bgr") -> np.ndarray:
 
 
 class Decoder:
-    """Baseline JFIF streams (the shape encoder.c:549-644 writes) -> the
-    encoder's coefficient planes, entropy-decoded on the GPU, and from those
-    (reconstruct) the pixels libjpeg would give."""
+    """Baseline JPEG streams (the encoder's own three-scan shape, and what
+    libjpeg writes: one interleaved scan, greyscale / 4:4:4 / 4:2:2 / 4:2:0,
+    any size, restart intervals) -> coefficient planes, entropy-decoded on
+    the GPU, and from those (reconstruct) the pixels libjpeg would give."""
 
     def __init__(self, max_w: int, max_h: int, max_frames: int, device: int = 0):
         self.lib = load()
@@ -940,6 +945,31 @@ class Decoder:
         Cr = np.zeros(w * h // 4, np.int16)
         _check(self.lib.mij_decoder_coefs(self.h_, frame, _ptr(Y), _ptr(Cb), _ptr(Cr)), "decoder_coefs")
         return Y, Cb, Cr
+
+    def layout(self, frame: int) -> dict:
+        """mij_decoder_layout: the frame's geometry; "raw" is the int list as the library gives it"""
+        out = np.zeros(24, np.int32)
+        _check(self.lib.mij_decoder_layout(self.h_, frame, _ptr(out), out.size), "decoder_layout")
+        v = [int(x) for x in out]
+        keys = ("w", "h", "ncomp", "hmax", "vmax", "mcus_x", "mcus_y", "ri", "interleaved")
+        lay = dict(zip(keys, v[:9]))
+        lay["comps"] = [tuple(v[9 + 5 * c:14 + 5 * c]) for c in range(lay["ncomp"])]  # h, v, tq, bw, bh
+        lay["raw"] = v[:9 + 5 * lay["ncomp"]]
+        return lay
+
+    def component(self, frame: int, comp: int) -> np.ndarray:
+        """(blocks, 64) int16: the component's padded plane, zigzag order, absolute DC"""
+        _, _, _, bw, bh = self.layout(frame)["comps"][comp]
+        out = np.zeros((bw * bh, 64), np.int16)
+        _check(self.lib.mij_decoder_component(self.h_, frame, comp, _ptr(out), out.size), "decoder_component")
+        return out
+
+    def plane(self, frame: int, comp: int) -> np.ndarray:
+        """(8 * blocks down, 8 * blocks across) uint8: the padded sample plane after the IDCT"""
+        _, _, _, bw, bh = self.layout(frame)["comps"][comp]
+        out = np.zeros((8 * bh, 8 * bw), np.uint8)
+        _check(self.lib.mij_decoder_plane(self.h_, frame, comp, _ptr(out), out.nbytes), "decoder_plane")
+        return out
 
     def reconstruct(self, order: str = "bgr") -> None:
         """every frame of the last decode -> planes and pixels (asynchronous)"""

@@ -1,0 +1,154 @@
+"""Ordinary baseline JPEG files without a GPU (DESIGN.md "Decoding ordinary
+baseline files").
+
+The chain: Pillow's libjpeg-turbo == the plain Python decoder
+(foreign_model.py) == the committed digests (tests/golden/foreign/
+manifest.json, for machines without Pillow) == the kernels' own arithmetic
+(csrc/mij_pixels.h) run on the host.  The GPU side is
+tests/test_foreign_decode.py."""
+import ctypes as C
+import hashlib
+import io
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import foreign_cases as FC
+import mijpeg
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(REPO, "jpeg-encoder-decoder_amd")
+
+
+@pytest.mark.parametrize("name", FC.NAMES + sorted(FC.MANIFEST["rejects"]))
+def test_fixture_is_the_manifests(name):
+    e = FC.MANIFEST["files"].get(name) or FC.MANIFEST["rejects"][name]
+    b = FC.jpg(name)
+    assert len(b) == e["bytes"] and hashlib.sha256(b).hexdigest() == e["sha256"]
+    assert len(b) <= 12 * 1024
+
+
+@pytest.mark.parametrize("name", FC.NAMES)
+def test_model_equals_committed_digests(name):
+    m, e = FC.model(name), FC.MANIFEST["files"][name]
+    assert (m.w, m.h) == (e["w"], e["h"])
+    assert FC.sha(m.y) == e["y_sha256"]
+    assert FC.sha(m.rgb) == e["rgb_sha256"]
+    assert (m.bgr == m.rgb[..., ::-1]).all()
+
+
+@pytest.mark.parametrize("name", FC.NAMES)
+def test_model_equals_libjpeg(name):
+    try:
+        from PIL import Image, features
+    except ImportError:
+        pytest.skip("Pillow not installed")
+    if not features.check_feature("libjpeg_turbo"):
+        pytest.skip("Pillow without libjpeg-turbo")
+    m = FC.model(name)
+    ref = np.asarray(Image.open(io.BytesIO(FC.jpg(name))).convert("RGB"))
+    assert ref.shape == m.rgb.shape
+    assert (ref == m.rgb).all(), int((ref != m.rgb).any(-1).sum())
+
+
+def test_cases_pin_what_they_are_for():
+    """marker structure and switch points the fixtures exist for"""
+    L = {n: FC.model(n).layout for n in FC.NAMES}
+    assert L["420_70x37_rst1"][5:8] == [5, 3, 1] and L["420_70x37_rstrow"][7] == 5
+    assert L["420_1040x520_q30_rst4"][7] == 4 * 65 and L["420_1040x520_q30"][7] == 0
+    assert len(FC.model("420_1040x520_q30").coefs[0]) == 130 * 66 > 8192  # more than one DC tile of luma
+    assert FC.jpg("420_33x17_opt") != FC.jpg("420_35x21") and len(FC.jpg("420_33x17_opt")) < 600  # own tables
+    # replication vs fancy at downsampled width 2 / 3
+    assert [FC.pix_mode(FC.model(n).G) for n in ("420_4x4", "420_5x5", "422_3x8", "422_4x8", "422_5x8")] == \
+        [5, 4, 3, 3, 2]
+    for n in ("420_4x4", "422_3x8", "422_4x8"):
+        m = FC.model(n)
+        cb = m.planes[1][:m.h if "422" in n else (m.h + 1) // 2, :(m.w + 1) // 2]
+        assert len(np.unique(cb)) > 1  # the chroma is not flat, so replication and fancy differ
+    # blocks longer than one 512-bit chunk
+    nz = (FC.model("444_24x24_noise_q100").coefs[0] != 0).sum(1)
+    assert nz.min() > 55
+
+
+@pytest.fixture(scope="module")
+def pixels_check(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("foreign_pixels_check") / "foreign_pixels_check")
+    subprocess.check_call(["g++", "-O2", "-Wall", "-Werror", "-I" + os.path.join(PKG, "csrc"), "-o", exe,
+                           os.path.join(REPO, "tests", "foreign_pixels_check.cpp")])
+    return exe
+
+
+@pytest.mark.parametrize("name", FC.SMALL)
+def test_kernel_arithmetic_on_the_host_equals_model(name, pixels_check, tmp_path):
+    """idct_block and colour_tile_any (what k_il_idct and k_il_colour call),
+    compiled for the host and driven unit by unit as the kernels drive them"""
+    m = FC.model(name)
+    src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
+    with open(src, "wb") as f:
+        f.write(np.array([m.w, m.h, m.G["ncomp"], FC.pix_mode(m.G)], np.int32).tobytes())
+        for c, comp in enumerate(m.G["comps"]):
+            f.write(np.array([comp[3], comp[4]], np.int32).tobytes())
+            f.write(m.dqt[c].astype(np.int32).tobytes())
+        for a in m.coefs:
+            f.write(np.ascontiguousarray(a, np.int16).tobytes())
+    subprocess.check_call([pixels_check, str(src), str(dst)])
+    got = np.fromfile(dst, np.uint8)
+    planes = np.concatenate([p.ravel() for p in m.planes])
+    n = planes.size
+    assert (got[:n] == planes).all()
+    px = 3 * m.w * m.h
+    assert got.size == n + 2 * px
+    assert (got[n:n + px] == m.rgb.ravel()).all(), name
+    assert (got[n + px:] == m.bgr.ravel()).all(), name
+
+
+def _refuses(jpg: bytes):
+    """mij_decode with no room: the headers are judged before any device use"""
+    lib = mijpeg.load()
+    buf = np.frombuffer(jpg, np.uint8)
+    probe = np.zeros(1, np.uint8)
+    w, h = C.c_int(0), C.c_int(0)
+    rc = lib.mij_decode(buf.ctypes.data, buf.size, 1, probe.ctypes.data, 0, C.byref(w), C.byref(h))
+    return rc, lib.mij_last_message().decode()
+
+
+@pytest.mark.parametrize("name", sorted(FC.rejects()))
+def test_parser_refuses(name):
+    jpg, word = FC.rejects()[name]
+    rc, msg = _refuses(jpg)
+    assert rc == 8, (rc, msg)  # MIJ_EJPEG
+    assert "stream 0" in msg and word.lower() in msg.lower(), msg
+
+
+@pytest.mark.parametrize("name", FC.NAMES)
+def test_parser_accepts_and_reports_the_size(name):
+    rc, msg = _refuses(FC.jpg(name))
+    e = FC.MANIFEST["files"][name]
+    assert rc == 4 and str(3 * e["w"] * e["h"]) in msg, (rc, msg)  # MIJ_ENOSPC: accepted, size known
+
+
+def test_parser_refuses_other_layouts():
+    """sampling the decoder has no upsampler for, and scans it cannot place"""
+    base = bytearray(FC.jpg("420_35x21"))
+    sof = FC._segment(bytes(base), 0xC0)
+    for hv, word in ((0x12, "sampling"), (0x41, "sampling")):
+        e = bytearray(base)
+        e[sof + 11] = hv  # the first component's H/V
+        rc, msg = _refuses(bytes(e))
+        assert rc == 8 and word in msg, msg
+    e = bytearray(base)
+    e[sof + 14] = 0x21  # chroma 2x1
+    rc, msg = _refuses(bytes(e))
+    assert rc == 8 and "sampling" in msg, msg
+    e = bytearray(base)
+    sos = FC._segment(bytes(base), 0xDA)
+    e[sos + 4 + 1 + 6 + 1] = 62  # Se
+    rc, msg = _refuses(bytes(e))
+    assert rc == 8 and "Ss/Se" in msg, msg
+    # restart markers without a DRI
+    rst = FC.jpg("420_70x37_rst1")
+    d = FC._segment(rst, 0xDD)
+    rc, msg = _refuses(rst[:d] + rst[d + 6:])
+    assert rc == 8 and "restart" in msg.lower(), msg
