@@ -256,6 +256,56 @@ int mij_batch_upload_regions(mij_batch *b, const uint8_t *bgr, int stride_px, in
 int mij_encode_regions(const uint8_t *bgr, int stride_px, int frame_h, const area_t *regions,
                        int n, int quality, uint8_t *out, size_t cap, size_t *lens);
 
+/* ---- frames of any size: the interleaved output format -----
+ * The calls above write the reference's shape: width and height multiples of
+ * 16, three one-component scans.  These write what every other baseline
+ * encoder writes, for any 1 <= w, h <= 65535 inside the batch canvas: the
+ * frame is edge-extended to multiples of 16 (last column, then last row,
+ * replicated), colour conversion, 4:2:0, DCT, quantisation and zigzag are
+ * those of the calls above on the extended frame, SOF0 carries the true w and
+ * h, and the entropy data is ONE interleaved scan (MCU = Y Y Y Y Cb Cr, DC
+ * prediction per component in that order) with its own four optimised
+ * tables.  restart_rows = r > 0 adds a DRI of Ri = r * ceil(w / 16) MCUs and
+ * RSTn markers every r MCU rows (each interval padded with 1-bits, prediction
+ * back to 0); 0: none.  Every 0xFF of entropy data, pad bytes included, is
+ * followed by 0x00.  mij_decoder_decode / mij_decode read these streams. */
+
+/* Worst-case size of such a stream: that of the padded frame, 2 bytes per
+ * restart marker, the DRI segment.  0 for sizes outside 1..65535 or
+ * Ri > 65535. */
+size_t mij_max_jpg_bytes_any(int w, int h, int restart_rows);
+/* n device-resident frames of any size, pointer alignment and pitch (frame i
+ * at d_px + i*frame_stride, rows pitch bytes apart, wh = {w0, h0, w1, h1,
+ * ...}, sizes may differ) edge-extended into slots 0..n-1 in one launch; the
+ * padded sizes become the frame dims (as with mij_batch_gather_regions) and
+ * the true sizes are remembered for mij_batch_encode_interleaved.  With
+ * mij_batch_set_rgb on, the source bytes are R, G, B (set it before this
+ * call).  A later mij_batch_upload, _set_input, _set_frame_dims or region
+ * call forgets the true sizes.  The source is read in aligned 4-byte words:
+ * up to 3 bytes before d_px and up to 3 bytes past the last row's last pixel
+ * may be read (never used), always inside an aligned word that also holds
+ * bytes of the frame, so inside its allocation's pages. */
+int mij_batch_pad_input(mij_batch *b, const void *d_px, long long frame_stride, long long pitch,
+                        const int *wh, int n);
+/* the same for one host frame of stride_px pixels per row into slot `slot`;
+ * the other slots keep what they hold */
+int mij_batch_upload_any(mij_batch *b, const uint8_t *px, int stride_px, int w, int h, int slot);
+/* slots 0..nframes-1 (all holding padded input: MIJ_EINVAL otherwise, and
+ * for Ri > 65535) to interleaved streams; asynchronous on the batch's stream;
+ * results through mij_batch_output / _lengths / _tables, and the padded
+ * frames' coefficient planes through mij_batch_coefs.  A frame that fails
+ * (tables, capacity) has length 0 and its error code.  The first use
+ * allocates this format's buffers and, with restart intervals, grows the
+ * per-frame output capacity to mij_max_jpg_bytes_any of the canvas. */
+int mij_batch_encode_interleaved(mij_batch *b, int nframes, int restart_rows);
+/* One call, host to host, mirror of mij_decode: px holds w x h pixels in
+ * `order` (MIJ_PIX_BGR / MIJ_PIX_RGB), rows stride_px pixels apart.  *out_len
+ * (may be NULL) receives the stream's size, or with MIJ_ENOSPC -- returned
+ * before any device work when cap < mij_max_jpg_bytes_any(w, h,
+ * restart_rows), so cap 0 asks for it -- that bound. */
+int mij_encode_any(const uint8_t *px, int stride_px, int w, int h, int order, int quality,
+                   int restart_rows, uint8_t *out, size_t cap, size_t *out_len);
+
 /* ---- PPM ingest -----------------------------------
  * Header rules of the reference's reader, utils/original.c:294-365, kept
  * exactly: "P6" then a newline straight after it; then lines up to the first

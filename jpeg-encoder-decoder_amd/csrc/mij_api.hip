@@ -13,6 +13,7 @@
 
 #include "mij_host.h"
 #include "mij_internal.h"
+#include "mij_interleave.h"
 #include "mijpeg.h"
 #include "mij_testing.h"
 
@@ -385,6 +386,17 @@ struct mij_batch {
   long long steps = 0;
   int last_frames = 0;
   int plan[MIJ_PLAN_FIELDS] = {};  // mij_test_last_plan (csrc/mij_testing.h): the last encode's launch plan
+  // interleaved output format (mij_batch_pad_input / _upload_any /
+  // _encode_interleaved): per slot {true w, true h, swapped to B G R at pad
+  // time, -}, w == 0: no padded input; the device buffers exist from the
+  // first use on (il_ensure)
+  std::vector<int4> il_slot;
+  long long out_cap0 = 0;  // the geometry's output capacity (g.out_cap grows with restart markers)
+  int2 *d_il_tdims = nullptr;
+  uint16_t *d_il_blk_bits = nullptr;
+  uint32_t *d_il_mcu_off = nullptr, *d_il_row_bits = nullptr, *d_il_ffc = nullptr;
+  uint64_t *d_il_row_pre = nullptr, *d_il_ival = nullptr, *d_il_row_off = nullptr;
+  int *d_il_hdr = nullptr;
 };
 
 template <class T>
@@ -409,7 +421,8 @@ static void batch_free(mij_batch *b) {
                   b->d_scan_bits, b->d_out_len, b->d_hc, b->d_out, b->d_err, b->d_replays,
                   b->d_dcpred, b->d_bitbase, b->d_stage, b->d_fixmask, b->d_audit, b->d_ffc, b->d_choff, b->d_scan_base,
                   b->d_seam, b->d_pack_state, b->d_pack_ticket, b->d_fdims, b->d_frame, b->d_regions, b->d_pieces,
-                  b->d_bound_acc, b->d_dcx};
+                  b->d_bound_acc, b->d_dcx, b->d_il_tdims, b->d_il_blk_bits, b->d_il_mcu_off, b->d_il_row_bits,
+                  b->d_il_ffc, b->d_il_row_pre, b->d_il_ival, b->d_il_row_off, b->d_il_hdr};
   for (void *p : ptrs)
     if (p) hipFree(p);
   for (auto &row : b->evh)
@@ -443,6 +456,7 @@ static int batch_init(mij_batch *b, int device, int w, int h, int frames, int qu
   HIP_TRY(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
   b->own_stream = b->stream;
   b->g = make_geom(w, h);
+  b->out_cap0 = b->g.out_cap;
   b->cap = frames;
   b->quality = quality;
   const Geom &g = b->g;
@@ -571,6 +585,7 @@ extern "C" int mij_batch_set_stream(mij_batch *b, void *stream) {
 // slots first..first+n-1 hold canvas-sized frames again; a region batch
 // whose slots are then all canvas-sized is a plain batch
 static int canvas_frames(mij_batch *b, int first, int n) {
+  for (int i = first; i < first + n && i < (int)b->il_slot.size(); i++) b->il_slot[i].x = 0;  // true sizes forgotten
   if (!b->use_fdims) return MIJ_OK;
   const int2 cv = make_int2(b->g.w, b->g.h);
   for (int i = first; i < first + n; i++) b->h_fdims[i] = cv;
@@ -611,6 +626,7 @@ extern "C" int mij_batch_set_input(mij_batch *b, const void *d_bgr, long long fr
   HIP_TRY(hipSetDevice(b->dev));
   if (b->own_in && b->d_in) HIP_TRY(hipFree(b->d_in));
   b->own_in = false;
+  b->il_slot.clear();
   b->use_fdims = false;  // full frames: the batch geometry again
   b->d_in = (uint8_t *)d_bgr;
   b->in_fs = frame_stride;
@@ -1146,6 +1162,7 @@ static int upload_frame_dims(mij_batch *b, const int2 *wh, int n) {
 extern "C" int mij_batch_set_frame_dims(mij_batch *b, const int *wh, int nframes) {
   if (!b) return fail(MIJ_EINVAL, "set_frame_dims: null batch");
   HIP_TRY(hipSetDevice(b->dev));
+  b->il_slot.clear();  // (padded input: its true sizes are forgotten)
   if (!wh) {
     b->use_fdims = false;
     return MIJ_OK;
@@ -1179,6 +1196,7 @@ static int gather_regions(mij_batch *b, const uint8_t *d_src, long long src_pitc
     wh[i] = make_int2(d.w, d.h);
     max_h = d.h > max_h ? d.h : max_h;
   }
+  b->il_slot.clear();
   HIP_TRY(hipMemcpyAsync(b->d_regions, r.data(), sizeof(int4) * n, hipMemcpyHostToDevice, b->stream));
   HIP_TRY(launch_gather_regions(b->d_in, b->in_fs, b->pitch, d_src, src_pitch, b->d_regions, n, max_h,
                                 b->stream));
@@ -2203,5 +2221,258 @@ extern "C" int mij_colour_lut(uint32_t *out) {
   HIP_TRY(hipStreamSynchronize(b->stream));
   HIP_TRY(hipMemcpy(out, &b->d_tab->lut[0][0], sizeof(uint32_t) * 3 * LUT_WORDS,
                     hipMemcpyDeviceToHost));
+  return MIJ_OK;
+}
+
+// ---------------------------------------------------------------------------
+// interleaved output format: frames of any size, one
+// interleaved scan over MCU-padded planes, restart intervals of MCU rows
+// ---------------------------------------------------------------------------
+static int il_round16(int v) { return (v + 15) & ~15; }
+
+// restart markers of a w x h frame (h16 padded) at restart_rows; -1: Ri > 65535
+static long long il_markers(int w, int h, int restart_rows) {
+  if (restart_rows <= 0) return 0;
+  if ((long long)restart_rows * (il_round16(w) / 16) > 65535) return -1;
+  const long long rows = il_round16(h) / 16;
+  return (rows + restart_rows - 1) / restart_rows - 1;
+}
+
+extern "C" size_t mij_max_jpg_bytes_any(int w, int h, int restart_rows) {
+  if (w < 1 || h < 1 || w > 65535 || h > 65535 || restart_rows < 0) return 0;
+  const long long mk = il_markers(w, h, restart_rows);
+  if (mk < 0) return 0;
+  return (size_t)(make_geom(il_round16(w), il_round16(h)).out_cap + 2 * mk + (restart_rows ? 6 : 0));
+}
+
+// the buffers only this format needs; allocated at its first use
+static int il_ensure(mij_batch *b) {
+  if ((int)b->il_slot.size() != b->cap) b->il_slot.assign((size_t)b->cap, make_int4(0, 0, 0, 0));
+  if (b->d_il_tdims) return MIJ_OK;
+  const Geom &g = b->g;
+  const long long F = b->cap, rs = il_rows(g) + 1;
+  HIP_TRY(dalloc(&b->d_il_tdims, F));
+  HIP_TRY(dalloc(&b->d_il_blk_bits, F * g.nblk));
+  HIP_TRY(dalloc(&b->d_il_mcu_off, F * g.nC));
+  HIP_TRY(dalloc(&b->d_il_row_bits, F * il_rows(g)));
+  HIP_TRY(dalloc(&b->d_il_row_pre, F * rs));
+  HIP_TRY(dalloc(&b->d_il_ival, F * rs));
+  HIP_TRY(dalloc(&b->d_il_row_off, F * rs));
+  HIP_TRY(dalloc(&b->d_il_ffc, F * il_chunks(g)));
+  HIP_TRY(dalloc(&b->d_il_hdr, F));
+  return MIJ_OK;
+}
+
+static int il_check_size(const mij_batch *b, int w, int h, const char *what, int i) {
+  if (w < 1 || h < 1 || w > 65535 || h > 65535 || il_round16(w) > b->g.w || il_round16(h) > b->g.h)
+    return fail(MIJ_EINVAL, "%s: frame %d is %dx%d (1..65535, padded to 16 at most the batch's %dx%d)", what, i, w, h,
+                b->g.w, b->g.h);
+  return MIJ_OK;
+}
+
+// slots first .. first+n-1 now hold padded frames of true sizes wh[]: the
+// frame dims K1 sees are the padded sizes; a batch whose slots are all
+// canvas-sized stays a plain one
+static int il_set_slots(mij_batch *b, const int2 *wh, int first, int n, bool others_canvas) {
+  // a plain batch keeps no per-frame sizes: what h_fdims holds for the other
+  // slots is then left over from an earlier region batch, and they are canvas-sized
+  const bool reset_dims = others_canvas || !b->use_fdims;
+  for (int i = 0; i < b->cap; i++) {
+    if (i >= first && i < first + n) {
+      b->h_fdims[i] = make_int2(il_round16(wh[i - first].x), il_round16(wh[i - first].y));
+      b->il_slot[i] = make_int4(wh[i - first].x, wh[i - first].y, b->rgb ? 1 : 0, 0);
+    } else {
+      if (reset_dims) b->h_fdims[i] = make_int2(b->g.w, b->g.h);
+      if (others_canvas) b->il_slot[i].x = 0;
+    }
+  }
+  HIP_TRY(hipMemcpyAsync(b->d_fdims, b->h_fdims.data(), sizeof(int2) * b->cap, hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));  // pageable sources
+  bool all = true;
+  for (const int2 &d : b->h_fdims) all = all && d.x == b->g.w && d.y == b->g.h;
+  b->use_fdims = !all;
+  return MIJ_OK;
+}
+
+static int il_pad(mij_batch *b, const uint8_t *d_src, long long src_fs, long long src_pitch, int first, int n) {
+  IlPadArgs p;
+  p.dst = b->d_in + (long long)first * b->in_fs;
+  p.slot_bytes = b->in_fs;
+  p.pitch = b->pitch;
+  p.src = d_src;
+  p.src_fs = src_fs;
+  p.src_pitch = src_pitch;
+  p.tdims = b->d_il_tdims + first;
+  p.swap = b->rgb ? 1 : 0;
+  p.cw = b->g.w;
+  p.ch = b->g.h;
+  HIP_TRY(launch_il_pad(p, n, b->stream));
+  return MIJ_OK;
+}
+
+extern "C" int mij_batch_pad_input(mij_batch *b, const void *d_px, long long frame_stride, long long pitch,
+                                   const int *wh, int n) {
+  if (pipe_check(b, "pad_input")) return g_err;
+  if (!b->own_in) return fail(MIJ_EINVAL, "pad_input: batch reads external device input");
+  if (!d_px || !wh || n < 1 || n > b->cap || frame_stride < 0)
+    return fail(MIJ_EINVAL, "pad_input: null argument or bad frame count %d", n);
+  std::vector<int2> v(n);
+  for (int i = 0; i < n; i++) {
+    if (il_check_size(b, wh[2 * i], wh[2 * i + 1], "pad_input", i)) return g_err;
+    if (pitch < 3LL * wh[2 * i]) return fail(MIJ_EINVAL, "pad_input: pitch %lld under frame %d's 3*%d bytes", pitch, i, wh[2 * i]);
+    v[i] = make_int2(wh[2 * i], wh[2 * i + 1]);
+  }
+  HIP_TRY(hipSetDevice(b->dev));
+  if (il_ensure(b)) return g_err;
+  HIP_TRY(hipMemcpyAsync(b->d_il_tdims, v.data(), sizeof(int2) * n, hipMemcpyHostToDevice, b->stream));
+  if (il_pad(b, (const uint8_t *)d_px, frame_stride, pitch, 0, n)) return g_err;
+  return il_set_slots(b, v.data(), 0, n, true);  // synchronises (pageable sources)
+}
+
+extern "C" int mij_batch_upload_any(mij_batch *b, const uint8_t *px, int stride_px, int w, int h, int slot) {
+  if (pipe_check(b, "upload_any")) return g_err;
+  if (!b->own_in) return fail(MIJ_EINVAL, "upload_any: batch reads external device input");
+  if (!px || slot < 0 || slot >= b->cap) return fail(MIJ_EINVAL, "upload_any: null frame or bad slot %d", slot);
+  if (il_check_size(b, w, h, "upload_any", slot)) return g_err;
+  if (stride_px < w) return fail(MIJ_EINVAL, "upload_any: stride %d under the width %d", stride_px, w);
+  HIP_TRY(hipSetDevice(b->dev));
+  if (il_ensure(b)) return g_err;
+  const size_t bytes = (size_t)w * h * 3;
+  if (bytes > b->frame_cap) {
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (b->d_frame) HIP_TRY(hipFree(b->d_frame));
+    b->d_frame = nullptr;
+    b->frame_cap = 0;
+    HIP_TRY(hipMalloc((void **)&b->d_frame, bytes + 16));
+    b->frame_cap = bytes;
+  }
+  const int2 d = make_int2(w, h);
+  HIP_TRY(hipMemcpy2DAsync(b->d_frame, (size_t)w * 3, px, (size_t)stride_px * 3, (size_t)w * 3, h,
+                           hipMemcpyHostToDevice, b->stream));
+  HIP_TRY(hipMemcpyAsync(b->d_il_tdims + slot, &d, sizeof(int2), hipMemcpyHostToDevice, b->stream));
+  if (il_pad(b, b->d_frame, 0, 3LL * w, slot, 1)) return g_err;
+  return il_set_slots(b, &d, slot, 1, false);  // synchronises (pageable sources)
+}
+
+extern "C" int mij_batch_encode_interleaved(mij_batch *b, int nframes, int restart_rows) {
+  if (pipe_check(b, "encode_interleaved")) return g_err;
+  if (nframes < 1 || nframes > b->cap) return fail(MIJ_EINVAL, "encode_interleaved: bad frame count %d", nframes);
+  if (restart_rows < 0) return fail(MIJ_EINVAL, "encode_interleaved: restart_rows %d", restart_rows);
+  long long markers = 0;
+  for (int i = 0; i < nframes; i++) {
+    if (i >= (int)b->il_slot.size() || b->il_slot[i].x == 0)
+      return fail(MIJ_EINVAL, "encode_interleaved: slot %d holds no padded input (pad_input / upload_any first)", i);
+    const int4 s = b->il_slot[i];
+    if (s.z != (b->rgb ? 1 : 0))
+      return fail(MIJ_EINVAL, "encode_interleaved: set_rgb changed after slot %d was padded", i);
+    const long long mk = il_markers(s.x, s.y, restart_rows);
+    if (mk < 0)
+      return fail(MIJ_EINVAL, "encode_interleaved: restart interval of %d rows x %d MCUs = %lld MCUs, over 65535 (slot %d)",
+                  restart_rows, il_round16(s.x) / 16, (long long)restart_rows * (il_round16(s.x) / 16), i);
+    markers = std::max(markers, mk);
+  }
+  HIP_TRY(hipSetDevice(b->dev));
+  // the per-frame output capacity covers mij_max_jpg_bytes_any of the canvas
+  const long long need = round_up(b->out_cap0 + 2 * std::max(markers, il_markers(b->g.w, b->g.h, restart_rows)) +
+                                  (restart_rows ? 6 : 0), 256);
+  if (need > b->g.out_cap) {
+    // the new buffer first: a failed allocation leaves the batch as it was
+    uint8_t *grown = nullptr;
+    HIP_TRY(dalloc(&grown, (long long)b->cap * need));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    hipFree(b->d_out);
+    b->d_out = grown;
+    b->g.out_cap = need;
+  }
+  next_slot(b);
+  HIP_TRY(hipMemsetAsync(b->d_hist, 0, sizeof(uint32_t) * nframes * 4 * 257, b->stream));
+  HIP_TRY(hipMemsetAsync(b->d_err, 0, sizeof(int) * nframes, b->stream));
+  b->k1_err_zero = 0;
+  if (b->timing) HIP_TRY(hipEventRecord(b->ev[0], b->stream));
+  // K1 unchanged, coefficient mode, on the padded slots (already B, G, R)
+  const bool rgb = b->rgb;
+  b->rgb = false;
+  const int rc = run_k1(b, nframes, 1);  // events 1, 2
+  b->rgb = rgb;
+  if (rc) return g_err;
+  if (b->timing) HIP_TRY(hipEventRecord(b->ev[3], b->stream));
+  const EntArgs e = ent_args(b, nframes);  // (the tables' arguments; resets hist_zero_n)
+  b->band_hist_zero = 0;
+  IlArgs a;
+  memset(&a, 0, sizeof(a));
+  a.g = b->g;
+  a.nframes = nframes;
+  a.restart_rows = restart_rows;
+  a.pdims = b->d_fdims;
+  a.tdims = b->d_il_tdims;
+  a.coef = b->d_coef;
+  a.dc = b->d_dc;
+  a.hist = b->d_hist;
+  a.ehuf = b->d_ehuf;
+  a.hc = b->d_hc;
+  a.tab = b->d_tab;
+  a.blk_bits = b->d_il_blk_bits;
+  a.mcu_off = b->d_il_mcu_off;
+  a.row_bits = b->d_il_row_bits;
+  a.row_pre = (unsigned long long *)b->d_il_row_pre;
+  a.ival_off = (unsigned long long *)b->d_il_ival;
+  a.row_off = (unsigned long long *)b->d_il_row_off;
+  a.raw = b->d_raw;
+  a.ffc = b->d_il_ffc;
+  a.hdr = b->d_il_hdr;
+  a.out = b->d_out;
+  a.out_len = b->d_out_len;
+  a.err = b->d_err;
+  HIP_TRY(launch_il_hist(a, b->stream));
+  if (b->timing) HIP_TRY(hipEventRecord(b->ev[4], b->stream));
+  HIP_TRY(launch_tables(e, b->stream));  // k_tables_1w: the path mij_batch_build_tables takes
+  if (b->timing) HIP_TRY(hipEventRecord(b->ev[5], b->stream));
+  b->raw_dirty = std::max(b->raw_dirty, nframes);  // (the band paths need all-zero scan words)
+  HIP_TRY(launch_il_entropy(a, b->stream));
+  if (b->timing) {
+    HIP_TRY(hipEventRecord(b->ev[6], b->stream));
+    HIP_TRY(hipEventRecord(b->ev[7], b->stream));
+  }
+  b->last_frames = nframes;
+  return MIJ_OK;
+}
+
+// host to host, the mirror of mij_decode: one context, grown to the largest
+// frame seen.  The quantiser tables are built with the batch, so a call at
+// another quality makes a new context (a caller alternating qualities pays
+// that on every call; a batch per quality avoids it).
+static mij_batch *g_actx = nullptr;
+
+extern "C" int mij_encode_any(const uint8_t *px, int stride_px, int w, int h, int order, int quality,
+                              int restart_rows, uint8_t *out, size_t cap, size_t *out_len) {
+  std::lock_guard<std::mutex> l(g_mu);
+  g_err = MIJ_OK;
+  if (w < 1 || h < 1 || w > 65535 || h > 65535)
+    return fail(MIJ_EINVAL, "mij_encode_any: frame %dx%d (1..65535 each)", w, h);
+  if (quality < 1 || quality > 100 || (order != MIJ_PIX_BGR && order != MIJ_PIX_RGB) || restart_rows < 0)
+    return fail(MIJ_EINVAL, "mij_encode_any: quality %d, order %d or restart_rows %d out of range", quality, order,
+                restart_rows);
+  if (il_markers(w, h, restart_rows) < 0)
+    return fail(MIJ_EINVAL, "mij_encode_any: restart interval of %d rows x %d MCUs is over 65535 MCUs", restart_rows,
+                il_round16(w) / 16);
+  const size_t bound = mij_max_jpg_bytes_any(w, h, restart_rows);
+  if (out_len) *out_len = bound;
+  if (cap < bound) return fail(MIJ_ENOSPC, "mij_encode_any: need %zu bytes for %dx%d", bound, w, h);
+  if (!px || !out || stride_px < w) return fail(MIJ_EINVAL, "mij_encode_any: null buffer or stride %d under the width", stride_px);
+  const int W = il_round16(w), H = il_round16(h);
+  if (!g_actx || g_actx->g.w < W || g_actx->g.h < H || g_actx->quality != quality) {
+    const int cw = g_actx && g_actx->g.w > W ? g_actx->g.w : W;
+    const int ch = g_actx && g_actx->g.h > H ? g_actx->g.h : H;
+    batch_free(g_actx);
+    g_actx = mij_batch_create(drop_device(), cw, ch, 1, quality);
+    if (!g_actx) return g_err;
+  }
+  mij_batch *b = g_actx;
+  b->rgb = order == MIJ_PIX_RGB;
+  if (mij_batch_upload_any(b, px, stride_px, w, h, 0)) return g_err;
+  if (mij_batch_encode_interleaved(b, 1, restart_rows)) return g_err;
+  size_t n = 0;
+  if (mij_batch_output(b, 0, out, cap, &n)) return g_err;
+  if (out_len) *out_len = n;
   return MIJ_OK;
 }

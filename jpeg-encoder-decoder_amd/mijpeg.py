@@ -47,6 +47,8 @@ EXPORTS = [
     "mij_stream_encode_frames", "mij_stream_stats",
     "mij_batch_set_frame_dims", "mij_batch_gather_regions", "mij_batch_upload_regions",
     "mij_encode_regions",
+    "mij_max_jpg_bytes_any", "mij_batch_pad_input", "mij_batch_upload_any", "mij_batch_encode_interleaved",
+    "mij_encode_any",
 ]
 
 
@@ -230,6 +232,12 @@ def load() -> C.CDLL:
         lib.mij_decoder_layout.argtypes = [p, i, p, i]
         lib.mij_decoder_component.argtypes = [p, i, i, p, sz]
         lib.mij_decoder_plane.argtypes = [p, i, i, p, sz]
+        lib.mij_max_jpg_bytes_any.restype = sz
+        lib.mij_max_jpg_bytes_any.argtypes = [i, i, i]
+        lib.mij_batch_pad_input.argtypes = [p, p, C.c_longlong, C.c_longlong, p, i]
+        lib.mij_batch_upload_any.argtypes = [p, p, i, i, i, i]
+        lib.mij_batch_encode_interleaved.argtypes = [p, i, i]
+        lib.mij_encode_any.argtypes = [p, i, i, i, i, i, i, p, sz, C.POINTER(sz)]
     except AttributeError:
         if not os.environ.get("MIJ_LIB"):  # older builds only in A/B timing runs
             raise
@@ -351,6 +359,26 @@ def encode(frame_bgr: np.ndarray, quality: int = 50, region=None) -> bytes:
     return out[:n.value].tobytes()
 
 
+def max_jpg_bytes_any(w: int, h: int, restart_rows: int = 0) -> int:
+    return int(load().mij_max_jpg_bytes_any(w, h, restart_rows))
+
+
+def encode_any(frame: np.ndarray, order: str = "bgr", quality: int = 50, restart_rows: int = 0) -> bytes:
+    """mij_encode_any: an (h, w, 3) frame of any size to a standard
+    interleaved baseline stream, host to host."""
+    lib = load()
+    frame = np.ascontiguousarray(frame, np.uint8)
+    h, w = frame.shape[:2]
+    n = C.c_size_t(0)
+    rc = lib.mij_encode_any(None, w, w, h, PIXEL_ORDERS[order], quality, restart_rows, None, 0, C.byref(n))
+    if rc != 4:  # MIJ_ENOSPC carries the bound
+        _check(rc or 1, "mij_encode_any")
+    out = np.zeros(n.value, np.uint8)
+    _check(lib.mij_encode_any(_ptr(frame), w, w, h, PIXEL_ORDERS[order], quality, restart_rows, _ptr(out),
+                              out.size, C.byref(n)), "mij_encode_any")
+    return out[:n.value].tobytes()
+
+
 # ---- device-resident batch ---------------------------------------------------
 
 class Batch:
@@ -424,6 +452,29 @@ class Batch:
         _check(self.lib.mij_batch_gather_regions(self.h_, dev_ptr, pitch, frame_w, frame_h,
                                                  _areas(regions), len(regions)), "gather_regions")
         self.fdims = [(int(r[2]), int(r[3])) for r in regions]
+
+    def pad_input(self, dev_ptr: int, frame_stride: int, pitch: int, dims) -> None:
+        """device frames of any (w, h), alignment and pitch, edge-extended to
+        multiples of 16 into slots 0..n-1 (mij_batch_pad_input)"""
+        wh = np.ascontiguousarray(np.asarray(dims, np.int32).reshape(-1, 2))
+        _check(self.lib.mij_batch_pad_input(self.h_, dev_ptr, frame_stride, pitch, _ptr(wh), wh.shape[0]),
+               "pad_input")
+        self.fdims = [((int(w) + 15) & ~15, (int(h) + 15) & ~15) for w, h in wh]
+
+    def upload_any(self, frame: np.ndarray, slot: int = 0) -> None:
+        """one host (h, w, 3) frame of any size into a slot (mij_batch_upload_any)"""
+        frame = np.ascontiguousarray(frame, np.uint8)
+        h, w = frame.shape[:2]
+        _check(self.lib.mij_batch_upload_any(self.h_, _ptr(frame), w, w, h, slot), "upload_any")
+        dims = list(self.fdims) if self.fdims is not None else []
+        dims += [(self.w, self.h)] * max(0, self.max_frames - len(dims))
+        dims[slot] = ((w + 15) & ~15, (h + 15) & ~15)
+        self.fdims = dims
+
+    def encode_interleaved(self, n: int, restart_rows: int = 0) -> None:
+        """slots 0..n-1 (padded input) to one-interleaved-scan streams of
+        their true sizes; restart_rows MCU rows per restart interval (0: none)"""
+        _check(self.lib.mij_batch_encode_interleaved(self.h_, n, restart_rows), "encode_interleaved")
 
     def upload(self, frames_bgr: np.ndarray, first: int = 0) -> None:
         frames_bgr = np.ascontiguousarray(frames_bgr, np.uint8)
