@@ -527,7 +527,10 @@ void *mij_detector_stream(mij_detector *d);
  * quantized coefficients, DC as the coded difference (= rgb_to_dct's
  * output), so encode -> decode can be checked bit-exactly at any size.
  * Entropy decoding runs on the GPU, one lane per 512-bit chunk of every
- * scan, the chunks' entry states found by self-synchronisation. */
+ * scan, the chunks' entry states found by self-synchronisation.
+ * From the decoded planes the same object gives pixels
+ * (mij_decoder_reconstruct) and, without leaving the coefficient domain, a
+ * losslessly re-coded stream (mij_decoder_transcode), each on request. */
 typedef struct mij_decoder mij_decoder;
 mij_decoder *mij_decoder_create(int device, int max_w, int max_h, int max_frames);
 void mij_decoder_destroy(mij_decoder *d);
@@ -602,6 +605,48 @@ void *mij_decoder_stream(mij_decoder *d);
  * a pixels / planes / device_pixels call before reconstruct or after a newer
  * decode, MIJ_ENOSPC for a short cap (everywhere above) */
 int mij_decode(const uint8_t *jpg, size_t len, int order, uint8_t *out, size_t cap, int *w, int *h);
+
+/* ---- lossless transcoding ------------------------------------
+ * What jpegtran -optimize does, on the GPU: every frame of the last decode,
+ * of either kind above, becomes one standard interleaved baseline stream
+ * with the SAME quantized coefficients (the blocks of the MCU padding as
+ * decoded), sampling, size, component ids and DQT bytes; only the entropy
+ * code is rebuilt.  Huffman tables are optimised for the new scan (DC/AC of
+ * component 0, DC/AC of components 1 and 2 together; a greyscale file gets
+ * two), restart intervals are restart_rows whole MCU rows of the source's
+ * MCU grid (0: none; DRI = restart_rows * MCUs across, written whenever
+ * restart_rows > 0), whatever interval the source had.  Headers: SOI, the
+ * JFIF APP0 of mij_encode_any, one DQT per table id in use (ascending),
+ * DHTs, SOF0 with the source's component entries verbatim, DRI, one SOS.
+ * Every other segment of the source is DROPPED: APPn (EXIF, ICC, Adobe,
+ * the source's JFIF density), COM, its Huffman tables.  A three-scan stream
+ * of mij_encode becomes byte for byte what mij_encode_any writes for the
+ * same frame.  Decoding the result gives the source's coefficients, so any
+ * decoder gives the source's pixels.
+ *
+ * MIJ_EINVAL before any device work for restart_rows < 0 or an interval over
+ * 65535 MCUs in any frame (the message names it), and for a call before a
+ * successful decode.  The call waits for the device (the frames' bit counts
+ * size its buffers, which are allocated on first use and grow; a decoder
+ * that never transcodes allocates none).  It neither needs nor disturbs
+ * mij_decoder_reconstruct: both may follow one decode, in either order.  A
+ * frame whose tables cannot be built (MIJ_ETABLE from the two calls below,
+ * length 0) does not fail the others. */
+int mij_decoder_transcode(mij_decoder *d, int restart_rows);
+/* host copy of frame's stream; *len (may be NULL) its size, also with
+ * MIJ_ENOSPC (cap 0, dst NULL asks for it); waits.  MIJ_EINVAL before a
+ * transcode or after a newer decode */
+int mij_decoder_transcoded(mij_decoder *d, int frame, uint8_t *dst, size_t cap, size_t *len);
+/* device address and size of frame's stream, valid until the next decode or
+ * transcode; NULL (and mij_last_error) where the call above fails */
+void *mij_decoder_device_transcoded(mij_decoder *d, int frame, size_t *len);
+/* HIP-event time of the last transcode (ms), its mid-call wait for the bit
+ * counts included; waits */
+int mij_decoder_transcode_ms(mij_decoder *d, float *ms);
+/* one call, host to host; cap 0 asks for the size (MIJ_ENOSPC, the exact
+ * length in *out_len).  A stream the decoder refuses returns its MIJ_EJPEG
+ * and message */
+int mij_transcode(const uint8_t *jpg, size_t len, int restart_rows, uint8_t *out, size_t cap, size_t *out_len);
 
 /* Drop-in entry points of include/brain.h:7-10, on frames of
  * mij_set_input_stride() x mij_set_frame_height() pixels (define.h:3-4,

@@ -40,6 +40,7 @@
 
 #include "mij_host.h"
 #include "mij_pixels.h"
+#include "mij_transcode.h"
 
 #define HIP_TRY(x)                                                                 \
   do {                                                                             \
@@ -906,6 +907,7 @@ struct Parsed {
   int ncomp = 0;
   // components in SOF order; a single component is 1x1 whatever it declares
   int cid[3] = {0, 0, 0}, hs[3] = {1, 1, 1}, vs[3] = {1, 1, 1}, tq[3] = {0, 0, 0};
+  uint8_t decl_hv[3] = {0x11, 0x11, 0x11};  // SOF0's H/V bytes as declared (transcoding writes them back)
   int hmax = 1, vmax = 1, mcus_x = 0, mcus_y = 0;
   int bw[3] = {0, 0, 0}, bh[3] = {0, 0, 0};  // padded planes, in blocks
   int ri = 0;       // restart interval in MCUs, 0 = none
@@ -1016,6 +1018,7 @@ int parse(const uint8_t *s, size_t n, Parsed &P, int frame) {
       for (int c = 0; c < nc; c++) {
         const uint8_t *e = q + 6 + 3 * c;
         P.cid[c] = e[0];
+        P.decl_hv[c] = e[1];
         P.hs[c] = e[1] >> 4;
         P.vs[c] = e[1] & 15;
         P.tq[c] = e[2];
@@ -1229,6 +1232,37 @@ struct mij_decoder {
   std::vector<mij::IlRec> h_irec;
   std::vector<mij::IlPix> h_ipix;
   std::vector<int32_t> h_irecq;
+  // lossless transcoding (mij_decoder_transcode): everything allocated at its
+  // first call and grown like the arena.  It keeps its own DC prefix sums, so
+  // that it and reconstruct may run in either order, or alone.
+  bool tc_valid = false;  // the streams below are the last decode's
+  hipEvent_t tc_ev[2] = {nullptr, nullptr};
+  int32_t *t_dcl = nullptr, *t_dcf = nullptr;  // prefix sums of the legacy slots' / the arena's DCs
+  uint32_t *t_tile = nullptr;
+  mij::IlRec *t_rec = nullptr;
+  mij::TcDc *t_dcjobs = nullptr;
+  int16_t *t_abs = nullptr;
+  mij::TcFrame *t_frames = nullptr;
+  mij::TcOut *t_outs = nullptr;
+  uint32_t *t_hist = nullptr, *t_ehuf = nullptr;
+  mij::HuffCode *t_hc = nullptr;
+  uint16_t *t_blk_bits = nullptr;
+  uint32_t *t_mcu_off = nullptr, *t_row_bits = nullptr;
+  unsigned long long *t_row_pre = nullptr, *t_ival = nullptr, *t_row_off = nullptr, *t_bits = nullptr;
+  uint32_t *t_raw = nullptr, *t_ffc = nullptr;
+  int *t_hdr = nullptr, *t_err = nullptr;
+  uint8_t *t_out = nullptr;
+  uint64_t *t_len = nullptr;
+  size_t t_dcl_cap = 0, t_dcf_cap = 0, t_tile_cap = 0, t_rec_cap = 0, t_dcjobs_cap = 0, t_abs_cap = 0,
+         t_frames_cap = 0, t_outs_cap = 0, t_hist_cap = 0, t_ehuf_cap = 0, t_hc_cap = 0, t_blk_bits_cap = 0,
+         t_mcu_off_cap = 0, t_row_bits_cap = 0, t_row_pre_cap = 0, t_ival_cap = 0, t_row_off_cap = 0,
+         t_bits_cap = 0, t_raw_cap = 0, t_ffc_cap = 0, t_hdr_cap = 0, t_err_cap = 0, t_out_cap = 0, t_len_cap = 0;
+  std::vector<mij::IlRec> h_trec;  // kept: the uploads are asynchronous
+  std::vector<mij::TcDc> h_tdc;
+  std::vector<mij::TcFrame> h_tframes;
+  std::vector<mij::TcOut> h_touts;
+  std::vector<uint64_t> tc_len;    // per frame of the last transcode
+  std::vector<int> tc_err;
 };
 
 static void decoder_free(mij_decoder *d) {
@@ -1264,7 +1298,15 @@ static void decoder_free(mij_decoder *d) {
   hipFree(d->f_status);
   hipFree(d->f_rjobs);
   hipFree(d->f_rpix);
+  for (void *p : {(void *)d->t_dcl, (void *)d->t_dcf, (void *)d->t_tile, (void *)d->t_rec, (void *)d->t_dcjobs,
+                  (void *)d->t_abs, (void *)d->t_frames, (void *)d->t_outs, (void *)d->t_hist, (void *)d->t_ehuf,
+                  (void *)d->t_hc, (void *)d->t_blk_bits, (void *)d->t_mcu_off, (void *)d->t_row_bits,
+                  (void *)d->t_row_pre, (void *)d->t_ival, (void *)d->t_row_off, (void *)d->t_bits, (void *)d->t_raw,
+                  (void *)d->t_ffc, (void *)d->t_hdr, (void *)d->t_err, (void *)d->t_out, (void *)d->t_len})
+    hipFree(p);
   for (hipEvent_t e : d->rec_ev)
+    if (e) hipEventDestroy(e);
+  for (hipEvent_t e : d->tc_ev)
     if (e) hipEventDestroy(e);
   if (d->h_blob) hipHostFree(d->h_blob);
   if (d->stream) hipStreamDestroy(d->stream);
@@ -1472,6 +1514,7 @@ extern "C" int mij_decoder_decode(mij_decoder *d, const uint8_t *const *jpgs, co
   HIP_TRY(hipSetDevice(d->dev));
   d->n = 0;  // set to n only once every stream decoded cleanly
   d->rec_valid = false;  // pixels of an earlier decode are no longer served
+  d->tc_valid = false;   // nor its transcoded streams
   d->parsed.assign(n, Parsed());
   d->loc.assign(n, FrameLoc());
   // host work per stream in parallel: parse (finds the scan ends), then
@@ -1996,6 +2039,292 @@ extern "C" int mij_decoder_reconstruct_ms(mij_decoder *d, float ms[2]) {
   return MIJ_OK;
 }
 
+// ---------------------------------------------------------------------------
+// lossless transcoding: host side
+// ---------------------------------------------------------------------------
+static long long round_to(long long v, long long m) { return (v + m - 1) / m * m; }
+
+// Every frame of the last decode -> one interleaved baseline stream with the
+// same coefficients, sampling and DQTs, tables optimised for it and restart
+// intervals of restart_rows MCU rows.  Waits for the device twice: once for
+// the frames' bits (they size the scan words and the output), once at the
+// end for the lengths.
+extern "C" int mij_decoder_transcode(mij_decoder *d, int restart_rows) {
+  mij_clear_error();
+  if (!d) return mij_fail(MIJ_EINVAL, "decoder_transcode: no decoder");
+  if (d->n < 1) return mij_fail(MIJ_EINVAL, "decoder_transcode: no decoded frames");
+  const int n = d->n;
+  for (int f = 0; f < n; f++) {
+    const long long ri = (long long)restart_rows * d->parsed[f].mcus_x;
+    if (restart_rows < 0 || ri > 65535)
+      return mij_fail(MIJ_EINVAL, "decoder_transcode: frame %d: restart interval of %d rows x %d MCUs = %lld MCUs "
+                      "(0..65535)", f, restart_rows, d->parsed[f].mcus_x, ri);
+  }
+  HIP_TRY(hipSetDevice(d->dev));
+  for (hipEvent_t &e : d->tc_ev)
+    if (!e) HIP_TRY(hipEventCreate(&e));
+  // the previous call's uploads read the vectors below: let them finish first
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  d->tc_valid = false;
+  // sizes of the per-call arrays
+  long long nblk = 0, nmcu = 0, nrows = 0, dcl = 0, dcf = 0, tiles_l = 0, tiles_f = 0;
+  int ncl = 0, ncf = 0, max_nblk = 0, max_rows = 0, max_comp = 0;
+  for (int f = 0; f < n; f++) {
+    const Parsed &P = d->parsed[f];
+    const FrameLoc &L = d->loc[f];
+    long long fb = 0;
+    for (int c = 0; c < P.ncomp; c++) {
+      const long long nb = (long long)P.bw[c] * P.bh[c];
+      fb += nb;
+      (L.foreign ? dcf : dcl) = std::max(L.foreign ? dcf : dcl, L.off[c] / 64 + nb);
+      (L.foreign ? tiles_f : tiles_l) += (nb + mij::DC_TILE - 1) / mij::DC_TILE;
+      (L.foreign ? ncf : ncl)++;
+      max_comp = (int)std::max<long long>(max_comp, nb);
+    }
+    nblk += fb;
+    nmcu += (long long)P.mcus_x * P.mcus_y;
+    nrows += P.mcus_y;
+    max_nblk = (int)std::max<long long>(max_nblk, fb);
+    max_rows = std::max(max_rows, P.mcus_y);
+  }
+  if (nblk > 0x7fff0000LL) return mij_fail(MIJ_EINVAL, "decoder_transcode: too many blocks");
+  const int ncomp = ncl + ncf;
+#define TC_GROW(p, cnt)                                            \
+  if (int rc = grow(d->p, d->p##_cap, (size_t)(cnt))) return rc
+  TC_GROW(t_dcl, dcl);
+  TC_GROW(t_dcf, dcf);
+  TC_GROW(t_tile, tiles_l + tiles_f);
+  TC_GROW(t_rec, ncomp);
+  TC_GROW(t_dcjobs, ncomp);
+  TC_GROW(t_abs, nblk);
+  TC_GROW(t_frames, n);
+  TC_GROW(t_outs, n);
+  TC_GROW(t_hist, (size_t)n * 4 * 257);
+  TC_GROW(t_ehuf, (size_t)n * 1024);
+  TC_GROW(t_hc, (size_t)n * 4);
+  TC_GROW(t_blk_bits, nblk);
+  TC_GROW(t_mcu_off, nmcu);
+  TC_GROW(t_row_bits, nrows);
+  TC_GROW(t_row_pre, nrows + n);
+  TC_GROW(t_ival, nrows + n);
+  TC_GROW(t_row_off, nrows + n);
+  TC_GROW(t_bits, n);
+  TC_GROW(t_hdr, n);
+  TC_GROW(t_err, n);
+  TC_GROW(t_len, n);
+  // descriptors: the legacy frames' components first (k_il_dc runs once over
+  // each of the two coefficient buffers), a legacy plane as a 1x1 scan of
+  // MCUs one block wide that never resets
+  d->h_trec.assign(ncomp, mij::IlRec());
+  d->h_tdc.assign(ncomp, mij::TcDc());
+  d->h_tframes.assign(n, mij::TcFrame());
+  int il = 0, ifg = ncl;
+  long long tl = 0, tf = 0, ab = 0, b0 = 0, m0 = 0, r0 = 0;
+  for (int f = 0; f < n; f++) {
+    const Parsed &P = d->parsed[f];
+    const FrameLoc &L = d->loc[f];
+    mij::TcFrame &F = d->h_tframes[f];
+    memset(&F, 0, sizeof F);
+    F.ncomp = P.ncomp;
+    F.mcus_x = P.mcus_x;
+    F.mcus_y = P.mcus_y;
+    F.R = restart_rows > 0 && restart_rows < P.mcus_y ? restart_rows : P.mcus_y;
+    F.nint = (P.mcus_y + F.R - 1) / F.R;
+    F.ri = restart_rows * P.mcus_x;
+    F.blk0 = b0;
+    F.mcu0 = (int)m0;
+    F.row0 = (int)r0;
+    F.rowp0 = (int)r0 + f;
+    F.w = P.w;
+    F.h = P.h;
+    bool used[4] = {false, false, false, false};
+    for (int c = 0; c < P.ncomp; c++) {
+      const int nb = P.bw[c] * P.bh[c];
+      const int k = L.foreign ? ifg++ : il++;
+      long long &t0 = L.foreign ? tf : tl;
+      mij::IlRec &j = d->h_trec[k];
+      memset(&j, 0, sizeof j);
+      j.off = L.off[c];
+      j.nblocks = nb;
+      j.bw = P.bw[c];
+      j.tile0 = (int)t0;
+      j.hs = L.foreign ? P.hs[c] : 1;
+      j.vs = L.foreign ? P.vs[c] : 1;
+      j.mcus_x = L.foreign ? P.mcus_x : P.bw[c];
+      j.seg = L.foreign && P.ri ? (int)std::min<long long>((long long)P.ri * P.hs[c] * P.vs[c], nb) : nb;
+      mij::TcDc &q = d->h_tdc[k];
+      q.pre = (L.foreign ? d->t_dcf : d->t_dcl) + L.off[c] / 64;
+      q.tile = d->t_tile + (L.foreign ? tiles_l : 0) + t0;
+      q.abs = d->t_abs + ab;
+      q.nblocks = nb;
+      q.seg = j.seg;
+      q.hs = j.hs;
+      q.vs = j.vs;
+      q.mcus_x = j.mcus_x;
+      q.bw = j.bw;
+      q.dc_tile = mij::DC_TILE;
+      q.pad = 0;
+      t0 += (nb + mij::DC_TILE - 1) / mij::DC_TILE;
+      mij::TcComp &C = F.c[c];
+      C.plane = (L.foreign ? d->f_coef : d->d_coef) + L.off[c];
+      C.abs = q.abs;
+      C.hs = P.hs[c];
+      C.vs = P.vs[c];
+      C.bw = P.bw[c];
+      ab += nb;
+      F.bpm += P.hs[c] * P.vs[c];
+      // SOF0's entry verbatim: a lone component keeps the sampling it declared,
+      // which parse() replaced by 1x1 (P.decl_hv)
+      F.sof[c][0] = (uint8_t)P.cid[c];
+      F.sof[c][1] = P.decl_hv[c];
+      F.sof[c][2] = (uint8_t)P.tq[c];
+      if (!P.have_dqt[P.tq[c]]) return mij_fail(MIJ_EJPEG, "stream %d: DQT %d of component %d missing", f, P.tq[c], c);
+      used[P.tq[c]] = true;
+    }
+    for (int t = 0; t < 4; t++)
+      if (used[t]) {  // at most three components: at most three ids
+        F.dqt_id[F.ndqt] = (uint8_t)t;
+        memcpy(F.dqt[F.ndqt], P.dqt[t], 64);
+        F.ndqt++;
+      }
+    F.nblk = P.mcus_x * P.mcus_y * F.bpm;
+    b0 += F.nblk;
+    m0 += (long long)P.mcus_x * P.mcus_y;
+    r0 += P.mcus_y;
+  }
+  HIP_TRY(hipMemcpyAsync(d->t_rec, d->h_trec.data(), ncomp * sizeof(mij::IlRec), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->t_dcjobs, d->h_tdc.data(), ncomp * sizeof(mij::TcDc), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->t_frames, d->h_tframes.data(), n * sizeof(mij::TcFrame), hipMemcpyHostToDevice,
+                         d->stream));
+  HIP_TRY(hipMemsetAsync(d->t_hist, 0, sizeof(uint32_t) * n * 4 * 257, d->stream));
+  HIP_TRY(hipMemsetAsync(d->t_err, 0, sizeof(int) * n, d->stream));
+  HIP_TRY(hipEventRecord(d->tc_ev[0], d->stream));
+  // absolute DCs: the decoder's prefix sums over the source's scan order
+  if (ncl) {
+    hipLaunchKernelGGL(mij::k_il_dc, dim3((unsigned)tiles_l), dim3(mij::DC_T), 0, d->stream, d->t_rec, ncl, d->d_coef,
+                       d->t_dcl, d->t_tile);
+    hipLaunchKernelGGL(mij::k_dec_dcbase<mij::IlRec>, dim3((ncl + 63) / 64), dim3(64), 0, d->stream, d->t_rec, ncl,
+                       d->t_tile);
+  }
+  if (ncf) {
+    hipLaunchKernelGGL(mij::k_il_dc, dim3((unsigned)tiles_f), dim3(mij::DC_T), 0, d->stream, d->t_rec + ncl, ncf,
+                       d->f_coef, d->t_dcf, d->t_tile + tiles_l);
+    hipLaunchKernelGGL(mij::k_dec_dcbase<mij::IlRec>, dim3((ncf + 63) / 64), dim3(64), 0, d->stream, d->t_rec + ncl,
+                       ncf, d->t_tile + tiles_l);
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(mij::launch_tc_abs(d->t_dcjobs, ncomp, max_comp, d->stream));
+  mij::TcArgs a;
+  memset(&a, 0, sizeof a);
+  a.fr = d->t_frames;
+  a.o = d->t_outs;
+  a.nframes = n;
+  a.max_nblk = max_nblk;
+  a.max_rows = max_rows;
+  a.hist = d->t_hist;
+  a.ehuf = d->t_ehuf;
+  a.hc = d->t_hc;
+  a.blk_bits = d->t_blk_bits;
+  a.mcu_off = d->t_mcu_off;
+  a.row_bits = d->t_row_bits;
+  a.row_pre = d->t_row_pre;
+  a.ival_off = d->t_ival;
+  a.row_off = d->t_row_off;
+  a.bits = d->t_bits;
+  a.hdr = d->t_hdr;
+  a.out_len = d->t_len;
+  a.err = d->t_err;
+  HIP_TRY(mij::launch_tc_hist(a, d->stream));
+  mij::EntArgs e;  // k_tables_1w: one wave per table, all four of every frame
+  memset(&e, 0, sizeof e);
+  e.nframes = n;
+  e.hist = d->t_hist;
+  e.ehuf = d->t_ehuf;
+  e.hc = d->t_hc;
+  e.err = d->t_err;
+  HIP_TRY(mij::launch_tables(e, d->stream));
+  HIP_TRY(mij::launch_tc_sizes(a, d->stream));
+  // the frames' bits size the scan words, the chunks and the output:
+  // headers + entropy bytes, every one of them stuffed + markers + EOI
+  std::vector<unsigned long long> bits(n);
+  HIP_TRY(hipMemcpyAsync(bits.data(), d->t_bits, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  d->h_touts.assign(n, mij::TcOut());
+  long long raw = 0, out = 0, chunks = 0, max_chunks = 0;
+  for (int f = 0; f < n; f++) {
+    mij::TcOut &O = d->h_touts[f];
+    const long long nbytes = (long long)(bits[f] >> 3), nch = (nbytes + mij::TC_CH - 1) / mij::TC_CH;
+    O.raw0 = raw;
+    O.raw_words = round_to((long long)(bits[f] / 128 + 1) * 4, 64);
+    O.out0 = out;
+    O.out_cap = round_to(mij::TC_HDR_MAX + 2 * nbytes + 2LL * d->h_tframes[f].nint + 2, 256);
+    O.chunk0 = chunks;
+    raw += O.raw_words;
+    out += O.out_cap;
+    chunks += nch;
+    max_chunks = std::max(max_chunks, nch);
+  }
+  TC_GROW(t_raw, raw);
+  TC_GROW(t_out, out);
+  TC_GROW(t_ffc, chunks + 1);
+#undef TC_GROW
+  HIP_TRY(hipMemcpyAsync(d->t_outs, d->h_touts.data(), n * sizeof(mij::TcOut), hipMemcpyHostToDevice, d->stream));
+  a.max_chunks = (int)std::min<long long>(max_chunks, 1 << 20);
+  a.raw = d->t_raw;
+  a.ffc = d->t_ffc;
+  a.out = d->t_out;
+  HIP_TRY(mij::launch_tc_write(a, d->stream));
+  HIP_TRY(hipEventRecord(d->tc_ev[1], d->stream));
+  d->tc_len.assign(n, 0);
+  d->tc_err.assign(n, 0);
+  HIP_TRY(hipMemcpyAsync(d->tc_len.data(), d->t_len, n * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->tc_err.data(), d->t_err, n * sizeof(int), hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  d->tc_valid = true;
+  return MIJ_OK;
+}
+
+// the frame's stream once the last decode has been transcoded
+static int tc_frame(mij_decoder *d, int frame, const char *what) {
+  if (!d) return mij_fail(MIJ_EINVAL, "%s: no decoder", what);
+  if (!d->tc_valid) return mij_fail(MIJ_EINVAL, "%s: no mij_decoder_transcode since the last decode", what);
+  if (frame < 0 || frame >= d->n) return mij_fail(MIJ_EINVAL, "%s: frame %d of %d", what, frame, d->n);
+  if (d->tc_err[frame]) return mij_frame_fail(d->tc_err[frame], what, frame);
+  return MIJ_OK;
+}
+
+extern "C" int mij_decoder_transcoded(mij_decoder *d, int frame, uint8_t *dst, size_t cap, size_t *len) {
+  mij_clear_error();
+  if (len) *len = 0;
+  if (int rc = tc_frame(d, frame, "decoder_transcoded")) return rc;
+  const size_t nbytes = (size_t)d->tc_len[frame];
+  if (len) *len = nbytes;
+  if (cap < nbytes) return mij_fail(MIJ_ENOSPC, "decoder_transcoded: need %zu bytes", nbytes);
+  if (!dst) return mij_fail(MIJ_EINVAL, "decoder_transcoded: dst is NULL");
+  HIP_TRY(hipSetDevice(d->dev));
+  HIP_TRY(hipMemcpyAsync(dst, d->t_out + d->h_touts[frame].out0, nbytes, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  return MIJ_OK;
+}
+
+extern "C" void *mij_decoder_device_transcoded(mij_decoder *d, int frame, size_t *len) {
+  mij_clear_error();
+  if (len) *len = 0;
+  if (tc_frame(d, frame, "decoder_device_transcoded")) return nullptr;
+  if (len) *len = (size_t)d->tc_len[frame];
+  return d->t_out + d->h_touts[frame].out0;
+}
+
+extern "C" int mij_decoder_transcode_ms(mij_decoder *d, float *ms) {
+  mij_clear_error();
+  if (!d || !ms) return mij_fail(MIJ_EINVAL, "decoder_transcode_ms: bad args");
+  if (!d->tc_valid) return mij_fail(MIJ_EINVAL, "decoder_transcode_ms: no mij_decoder_transcode since the last decode");
+  HIP_TRY(hipSetDevice(d->dev));
+  HIP_TRY(hipEventSynchronize(d->tc_ev[1]));
+  HIP_TRY(hipEventElapsedTime(ms, d->tc_ev[0], d->tc_ev[1]));
+  return MIJ_OK;
+}
+
 extern "C" void *mij_decoder_stream(mij_decoder *d) { return d ? (void *)d->stream : nullptr; }
 
 extern "C" int mij_decode(const uint8_t *jpg, size_t len, int order, uint8_t *out, size_t cap, int *w, int *h) {
@@ -2013,6 +2342,25 @@ extern "C" int mij_decode(const uint8_t *jpg, size_t len, int order, uint8_t *ou
   int rc = mij_decoder_decode(d, &jpg, &len, 1);
   if (!rc) rc = mij_decoder_reconstruct(d, order);
   if (!rc) rc = mij_decoder_pixels(d, 0, out, cap, 0);
+  decoder_free(d);  // (leaves the failure's message in place)
+  return rc;
+}
+
+extern "C" int mij_transcode(const uint8_t *jpg, size_t len, int restart_rows, uint8_t *out, size_t cap,
+                             size_t *out_len) {
+  mij_clear_error();
+  if (out_len) *out_len = 0;
+  if (!jpg || (!out && cap)) return mij_fail(MIJ_EINVAL, "mij_transcode: NULL buffer");
+  Parsed P;  // the size first: the decoder is made for it
+  if (int rc = parse(jpg, len, P, 0)) return mij_fail(rc, "mij_transcode: %s", P.err);
+  if (restart_rows < 0 || (long long)restart_rows * P.mcus_x > 65535)
+    return mij_fail(MIJ_EINVAL, "mij_transcode: frame 0: restart interval of %d rows x %d MCUs (0..65535 MCUs)",
+                    restart_rows, P.mcus_x);
+  mij_decoder *d = mij_decoder_create(mij_drop_device(), (P.w + 15) / 16 * 16, (P.h + 15) / 16 * 16, 1);
+  if (!d) return mij_last_error();
+  int rc = mij_decoder_decode(d, &jpg, &len, 1);
+  if (!rc) rc = mij_decoder_transcode(d, restart_rows);
+  if (!rc) rc = mij_decoder_transcoded(d, 0, out, cap, out_len);
   decoder_free(d);  // (leaves the failure's message in place)
   return rc;
 }

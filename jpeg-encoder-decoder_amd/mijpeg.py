@@ -49,6 +49,8 @@ EXPORTS = [
     "mij_encode_regions",
     "mij_max_jpg_bytes_any", "mij_batch_pad_input", "mij_batch_upload_any", "mij_batch_encode_interleaved",
     "mij_encode_any",
+    "mij_decoder_transcode", "mij_decoder_transcoded", "mij_decoder_device_transcoded", "mij_decoder_transcode_ms",
+    "mij_transcode",
 ]
 
 
@@ -238,6 +240,12 @@ def load() -> C.CDLL:
         lib.mij_batch_upload_any.argtypes = [p, p, i, i, i, i]
         lib.mij_batch_encode_interleaved.argtypes = [p, i, i]
         lib.mij_encode_any.argtypes = [p, i, i, i, i, i, i, p, sz, C.POINTER(sz)]
+        lib.mij_decoder_transcode.argtypes = [p, i]
+        lib.mij_decoder_transcoded.argtypes = [p, i, p, sz, C.POINTER(sz)]
+        lib.mij_decoder_device_transcoded.restype = p
+        lib.mij_decoder_device_transcoded.argtypes = [p, i, C.POINTER(sz)]
+        lib.mij_decoder_transcode_ms.argtypes = [p, C.POINTER(C.c_float)]
+        lib.mij_transcode.argtypes = [p, sz, i, p, sz, C.POINTER(sz)]
     except AttributeError:
         if not os.environ.get("MIJ_LIB"):  # older builds only in A/B timing runs
             raise
@@ -949,6 +957,22 @@ def decode(jpg: bytes, order: str = "bgr") -> np.ndarray:
     return out
 
 
+def transcode(jpg: bytes, restart_rows: int = 0) -> bytes:
+    """mij_transcode: one baseline stream -> the same coefficients in one
+    interleaved scan with optimised Huffman tables and restart intervals of
+    restart_rows MCU rows (0: none), host to host; lossless"""
+    lib = load()
+    buf = np.frombuffer(jpg, np.uint8)
+    n = C.c_size_t(0)
+    out = np.zeros(len(jpg) + 4096, np.uint8)  # enough for most; the exact size comes back otherwise
+    rc = lib.mij_transcode(_ptr(buf), buf.size, restart_rows, _ptr(out), out.nbytes, C.byref(n))
+    if rc == 4 and n.value > out.nbytes:  # MIJ_ENOSPC
+        out = np.zeros(n.value, np.uint8)
+        rc = lib.mij_transcode(_ptr(buf), buf.size, restart_rows, _ptr(out), out.nbytes, C.byref(n))
+    _check(rc, "mij_transcode")
+    return out[:n.value].tobytes()
+
+
 class Decoder:
     """Baseline JPEG streams (the encoder's own three-scan shape, and what
     libjpeg writes: one interleaved scan, greyscale / 4:4:4 / 4:2:2 / 4:2:0,
@@ -1066,3 +1090,30 @@ class Decoder:
     def stream_ptr(self) -> int:
         """the decoder's hipStream_t (Batch.set_stream orders an encode behind a reconstruct)"""
         return int(self.lib.mij_decoder_stream(self.h_) or 0)
+
+    def transcode(self, restart_rows: int = 0) -> None:
+        """every frame of the last decode -> a losslessly re-coded interleaved
+        stream (mij_decoder_transcode); waits for the device"""
+        _check(self.lib.mij_decoder_transcode(self.h_, restart_rows), "decoder_transcode")
+
+    def transcoded(self, frame: int) -> bytes:
+        """host copy of `frame`'s stream of the last transcode"""
+        _, size = self.device_transcoded(frame)
+        n = C.c_size_t(0)
+        out = np.zeros(size, np.uint8)
+        _check(self.lib.mij_decoder_transcoded(self.h_, frame, _ptr(out), out.nbytes, C.byref(n)), "decoder_transcoded")
+        return out[:n.value].tobytes()
+
+    def device_transcoded(self, frame: int):
+        """(device address, bytes) of `frame`'s stream: valid until the next decode or transcode"""
+        n = C.c_size_t(0)
+        ptr = self.lib.mij_decoder_device_transcoded(self.h_, frame, C.byref(n))
+        if not ptr:
+            _check(self.lib.mij_last_error() or 1, "decoder_device_transcoded")
+        return int(ptr), int(n.value)
+
+    def transcode_ms(self) -> float:
+        """HIP-event milliseconds of the last transcode; waits for it"""
+        ms = C.c_float(0)
+        _check(self.lib.mij_decoder_transcode_ms(self.h_, C.byref(ms)), "decoder_transcode_ms")
+        return float(ms.value)
