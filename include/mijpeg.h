@@ -648,6 +648,51 @@ int mij_decoder_transcode_ms(mij_decoder *d, float *ms);
  * and message */
 int mij_transcode(const uint8_t *jpg, size_t len, int restart_rows, uint8_t *out, size_t cap, size_t *out_len);
 
+/* ---- lossless transforms --------------------------------------
+ * The other half of jpegtran, in the coefficient domain: flip, transpose,
+ * rotation by 90/180/270 and MCU-aligned crop of every frame of the last
+ * decode, then coded as mij_decoder_transcode codes it.  No coefficient is
+ * requantised: blocks move, coefficients inside them are transposed and
+ * change sign.  Order: crop, then the edge rule, then the operation.
+ *   crop (x, y, w, h) in source pixels: x a multiple of 8*Hmax, y of 8*Vmax,
+ *   w, h >= 1, inside the frame; the result is w x h, a partial last MCU
+ *   keeps the source's blocks beyond the crop.  NULL: the whole frame.
+ *   edge rule: an operation that mirrors the source's width (FLIP_H, ROT180,
+ *   TRANSVERSE, ROT270) needs it to be whole MCUs, one that mirrors its height
+ *   (FLIP_V, ROT180, TRANSVERSE, ROT90) likewise; otherwise the call is
+ *   refused (jpegtran -perfect) or, with MIJ_XF_TRIM, the dimension is cut
+ *   down to whole MCUs first (jpegtran -trim).
+ *   headers as mij_decoder_transcode writes them; a transposing operation
+ *   swaps width and height and the nibbles of every SOF0 H/V byte and
+ *   transposes every DQT.  APPn / COM segments are dropped, an EXIF
+ *   orientation with them.  restart_rows counts MCU rows of the OUTPUT.
+ * MIJ_EINVAL before any device work, naming the frame and the reason: an
+ * unknown op or flag bit; a crop that is misaligned, empty or outside the
+ * frame; a mirrored dimension that is not whole MCUs without MIJ_XF_TRIM, or
+ * of which nothing is left with it; a transposing operation on a frame with a
+ * component whose H != V (4:2:2: the decoder would refuse the result); an
+ * interval over 65535 MCUs of the output grid.  One refused frame refuses the
+ * call.  MIJ_XF_NONE without a crop is mij_decoder_transcode, byte for byte.
+ * The results are read with mij_decoder_transcoded, _device_transcoded and
+ * _transcode_ms: "the last transcode" there is the last transcode or
+ * transform.  The transformed planes live in buffers allocated at the first
+ * transform; the decoded planes stay as they are (reconstruct and transcode
+ * may follow). */
+enum { MIJ_XF_NONE = 0, MIJ_XF_FLIP_H, MIJ_XF_FLIP_V, MIJ_XF_TRANSPOSE, MIJ_XF_TRANSVERSE,
+       MIJ_XF_ROT90, MIJ_XF_ROT180, MIJ_XF_ROT270 };        /* jpegtran's JXFORM order; ROT90 is clockwise */
+enum { MIJ_XF_TRIM = 1 };                                    /* flags */
+int mij_decoder_transform(mij_decoder *d, int op, int flags, const area_t *crop, int restart_rows);
+/* one call, host to host, as mij_transcode: cap 0 asks for the size; the
+ * refusals above come before any device work */
+int mij_transform(const uint8_t *jpg, size_t len, int op, int flags, const area_t *crop,
+                  int restart_rows, uint8_t *out, size_t cap, size_t *out_len);
+/* EXIF orientation 1..8 of a stream (APP1 "Exif", IFD0 tag 0x0112); 1 when
+ * there is none or it is malformed.  Host only */
+int mij_exif_orientation(const uint8_t *jpg, size_t len);   /* 1..8; 1 when there is none; host only */
+/* the operation that makes an image of that orientation upright (NONE for
+ * anything outside 1..8) */
+int mij_orientation_op(int orientation);                    /* the op that makes it upright */
+
 /* Drop-in entry points of include/brain.h:7-10, on frames of
  * mij_set_input_stride() x mij_set_frame_height() pixels (define.h:3-4,
  * 320x240 by default).  subsample writes the PPM copy to f when f is not

@@ -41,6 +41,7 @@
 #include "mij_host.h"
 #include "mij_pixels.h"
 #include "mij_transcode.h"
+#include "mij_transform.h"
 
 #define HIP_TRY(x)                                                                 \
   do {                                                                             \
@@ -1261,8 +1262,14 @@ struct mij_decoder {
   std::vector<mij::TcDc> h_tdc;
   std::vector<mij::TcFrame> h_tframes;
   std::vector<mij::TcOut> h_touts;
-  std::vector<uint64_t> tc_len;    // per frame of the last transcode
+  std::vector<uint64_t> tc_len;    // per frame of the last transcode or transform
   std::vector<int> tc_err;
+  // lossless transforms (mij_decoder_transform): the
+  // transformed planes and absolute DCs, allocated at the first transform
+  int16_t *x_plane = nullptr, *x_abs = nullptr;
+  mij::XfFrame *x_frames = nullptr;
+  size_t x_plane_cap = 0, x_abs_cap = 0, x_frames_cap = 0;
+  std::vector<mij::XfFrame> h_xframes;
 };
 
 static void decoder_free(mij_decoder *d) {
@@ -1302,7 +1309,8 @@ static void decoder_free(mij_decoder *d) {
                   (void *)d->t_abs, (void *)d->t_frames, (void *)d->t_outs, (void *)d->t_hist, (void *)d->t_ehuf,
                   (void *)d->t_hc, (void *)d->t_blk_bits, (void *)d->t_mcu_off, (void *)d->t_row_bits,
                   (void *)d->t_row_pre, (void *)d->t_ival, (void *)d->t_row_off, (void *)d->t_bits, (void *)d->t_raw,
-                  (void *)d->t_ffc, (void *)d->t_hdr, (void *)d->t_err, (void *)d->t_out, (void *)d->t_len})
+                  (void *)d->t_ffc, (void *)d->t_hdr, (void *)d->t_err, (void *)d->t_out, (void *)d->t_len,
+                  (void *)d->x_plane, (void *)d->x_abs, (void *)d->x_frames})
     hipFree(p);
   for (hipEvent_t e : d->rec_ev)
     if (e) hipEventDestroy(e);
@@ -2044,22 +2052,99 @@ extern "C" int mij_decoder_reconstruct_ms(mij_decoder *d, float ms[2]) {
 // ---------------------------------------------------------------------------
 static long long round_to(long long v, long long m) { return (v + m - 1) / m * m; }
 
+// One frame's output geometry: the source's own for a plain transcode, the
+// transformed image's for mij_decoder_transform.
+struct XfPlan {
+  int bits = 0;                // mij::XF_T | XF_FH | XF_FV
+  int w = 0, h = 0;            // SOF0's size
+  int mcus_x = 0, mcus_y = 0;
+  int hs[3] = {1, 1, 1}, vs[3] = {1, 1, 1};
+  int bw[3] = {0, 0, 0}, bh[3] = {0, 0, 0};  // the planes, in blocks
+  int ox[3] = {0, 0, 0}, oy[3] = {0, 0, 0};  // the crop's offset in the source planes, in blocks
+  uint8_t hv[3] = {0x11, 0x11, 0x11};        // SOF0's H/V bytes
+};
+
+// crop, then the edge rule, then the operation: decided from the markers
+// alone, before any device work.  MIJ_EINVAL names the frame and the reason.
+static int xf_plan(const Parsed &P, int op, int flags, const area_t *crop, int restart_rows, const char *who,
+                   int frame, XfPlan &X) {
+  static const char *const names[mij::XF_OPS] = {"NONE",       "FLIP_H", "FLIP_V", "TRANSPOSE",
+                                                 "TRANSVERSE", "ROT90",  "ROT180", "ROT270"};
+  if (op < 0 || op >= mij::XF_OPS) return mij_fail(MIJ_EINVAL, "%s: frame %d: unknown operation %d", who, frame, op);
+  if (flags & ~MIJ_XF_TRIM) return mij_fail(MIJ_EINVAL, "%s: frame %d: unknown flag bits 0x%x", who, frame, flags);
+  const int Mw = 8 * P.hmax, Mh = 8 * P.vmax;
+  int x = 0, y = 0, w = P.w, h = P.h;
+  if (crop) {
+    x = crop->x, y = crop->y, w = crop->w, h = crop->h;
+    if (w < 1 || h < 1) return mij_fail(MIJ_EINVAL, "%s: frame %d: empty crop %dx%d", who, frame, w, h);
+    if (x < 0 || y < 0 || (long long)x + w > P.w || (long long)y + h > P.h)
+      return mij_fail(MIJ_EINVAL, "%s: frame %d: crop %dx%d+%d+%d lies outside the %dx%d frame", who, frame, w, h, x,
+                      y, P.w, P.h);
+    if (x % Mw || y % Mh)
+      return mij_fail(MIJ_EINVAL, "%s: frame %d: crop offset +%d+%d is not aligned to the %dx%d MCU", who, frame, x,
+                      y, Mw, Mh);
+  }
+  X.bits = mij::xf_op_bits(op);
+  const bool T = X.bits & mij::XF_T;
+  if (T)
+    for (int c = 0; c < P.ncomp; c++)
+      if (P.hs[c] != P.vs[c])
+        return mij_fail(MIJ_EINVAL, "%s: frame %d: %s of a component with sampling %dx%d: the transposed %dx%d is "
+                        "not decodable here", who, frame, names[op], P.hs[c], P.vs[c], P.vs[c], P.hs[c]);
+  // mirrors of the SOURCE: the output's top-bottom flip after a transpose is the source's left-right one
+  const bool mir_h = X.bits & (T ? mij::XF_FV : mij::XF_FH), mir_v = X.bits & (T ? mij::XF_FH : mij::XF_FV);
+  if (mir_h && w % Mw) {
+    if (!(flags & MIJ_XF_TRIM))
+      return mij_fail(MIJ_EINVAL, "%s: frame %d: %s mirrors the width %d, which is not whole MCUs of %d "
+                      "(MIJ_XF_TRIM cuts it down)", who, frame, names[op], w, Mw);
+    if (w < Mw)
+      return mij_fail(MIJ_EINVAL, "%s: frame %d: %s with MIJ_XF_TRIM: nothing left of the width %d (MCUs of %d)",
+                      who, frame, names[op], w, Mw);
+    w = w / Mw * Mw;
+  }
+  if (mir_v && h % Mh) {
+    if (!(flags & MIJ_XF_TRIM))
+      return mij_fail(MIJ_EINVAL, "%s: frame %d: %s mirrors the height %d, which is not whole MCUs of %d "
+                      "(MIJ_XF_TRIM cuts it down)", who, frame, names[op], h, Mh);
+    if (h < Mh)
+      return mij_fail(MIJ_EINVAL, "%s: frame %d: %s with MIJ_XF_TRIM: nothing left of the height %d (MCUs of %d)",
+                      who, frame, names[op], h, Mh);
+    h = h / Mh * Mh;
+  }
+  const int smx = (w + Mw - 1) / Mw, smy = (h + Mh - 1) / Mh;  // the kept MCUs, in the source's orientation
+  X.w = T ? h : w;
+  X.h = T ? w : h;
+  X.mcus_x = T ? smy : smx;
+  X.mcus_y = T ? smx : smy;
+  for (int c = 0; c < P.ncomp; c++) {
+    X.hs[c] = T ? P.vs[c] : P.hs[c];
+    X.vs[c] = T ? P.hs[c] : P.vs[c];
+    X.bw[c] = X.mcus_x * X.hs[c];
+    X.bh[c] = X.mcus_y * X.vs[c];
+    X.ox[c] = x / Mw * P.hs[c];  // ox + kept blocks across <= P.bw: x + w <= P.w <= mcus_x * Mw
+    X.oy[c] = y / Mh * P.vs[c];
+    X.hv[c] = T ? (uint8_t)((P.decl_hv[c] << 4) | (P.decl_hv[c] >> 4)) : P.decl_hv[c];
+  }
+  const long long ri = (long long)restart_rows * X.mcus_x;
+  if (restart_rows < 0 || ri > 65535)
+    return mij_fail(MIJ_EINVAL, "%s: frame %d: restart interval of %d rows x %d MCUs = %lld MCUs (0..65535)", who,
+                    frame, restart_rows, X.mcus_x, ri);
+  return MIJ_OK;
+}
+
 // Every frame of the last decode -> one interleaved baseline stream with the
 // same coefficients, sampling and DQTs, tables optimised for it and restart
 // intervals of restart_rows MCU rows.  Waits for the device twice: once for
 // the frames' bits (they size the scan words and the output), once at the
 // end for the lengths.
-extern "C" int mij_decoder_transcode(mij_decoder *d, int restart_rows) {
-  mij_clear_error();
-  if (!d) return mij_fail(MIJ_EINVAL, "decoder_transcode: no decoder");
-  if (d->n < 1) return mij_fail(MIJ_EINVAL, "decoder_transcode: no decoded frames");
+//
+// The shared worker of mij_decoder_transcode and mij_decoder_transform (§4i):
+// plans[f] is frame f's output geometry; with xform the stage k_xf_blocks
+// writes transformed planes and absolute DCs between k_tc_abs and k_tc_hist
+// and the TcFrames point at those, without it they point at the decoded
+// planes and the plans are the source's own geometry.
+static int tc_run(mij_decoder *d, int restart_rows, const XfPlan *plans, bool xform, const char *who) {
   const int n = d->n;
-  for (int f = 0; f < n; f++) {
-    const long long ri = (long long)restart_rows * d->parsed[f].mcus_x;
-    if (restart_rows < 0 || ri > 65535)
-      return mij_fail(MIJ_EINVAL, "decoder_transcode: frame %d: restart interval of %d rows x %d MCUs = %lld MCUs "
-                      "(0..65535)", f, restart_rows, d->parsed[f].mcus_x, ri);
-  }
   HIP_TRY(hipSetDevice(d->dev));
   for (hipEvent_t &e : d->tc_ev)
     if (!e) HIP_TRY(hipEventCreate(&e));
@@ -2067,27 +2152,31 @@ extern "C" int mij_decoder_transcode(mij_decoder *d, int restart_rows) {
   HIP_TRY(hipStreamSynchronize(d->stream));
   d->tc_valid = false;
   // sizes of the per-call arrays
-  long long nblk = 0, nmcu = 0, nrows = 0, dcl = 0, dcf = 0, tiles_l = 0, tiles_f = 0;
+  // (src_nblk: the decoded planes' blocks; nblk, nmcu, nrows: the output's,
+  // never more than the source's)
+  long long src_nblk = 0, nblk = 0, nmcu = 0, nrows = 0, dcl = 0, dcf = 0, tiles_l = 0, tiles_f = 0;
   int ncl = 0, ncf = 0, max_nblk = 0, max_rows = 0, max_comp = 0;
   for (int f = 0; f < n; f++) {
     const Parsed &P = d->parsed[f];
     const FrameLoc &L = d->loc[f];
+    const XfPlan &X = plans[f];
     long long fb = 0;
     for (int c = 0; c < P.ncomp; c++) {
       const long long nb = (long long)P.bw[c] * P.bh[c];
-      fb += nb;
+      src_nblk += nb;
+      fb += (long long)X.bw[c] * X.bh[c];
       (L.foreign ? dcf : dcl) = std::max(L.foreign ? dcf : dcl, L.off[c] / 64 + nb);
       (L.foreign ? tiles_f : tiles_l) += (nb + mij::DC_TILE - 1) / mij::DC_TILE;
       (L.foreign ? ncf : ncl)++;
       max_comp = (int)std::max<long long>(max_comp, nb);
     }
     nblk += fb;
-    nmcu += (long long)P.mcus_x * P.mcus_y;
-    nrows += P.mcus_y;
+    nmcu += (long long)X.mcus_x * X.mcus_y;
+    nrows += X.mcus_y;
     max_nblk = (int)std::max<long long>(max_nblk, fb);
-    max_rows = std::max(max_rows, P.mcus_y);
+    max_rows = std::max(max_rows, X.mcus_y);
   }
-  if (nblk > 0x7fff0000LL) return mij_fail(MIJ_EINVAL, "decoder_transcode: too many blocks");
+  if (src_nblk > 0x7fff0000LL) return mij_fail(MIJ_EINVAL, "%s: too many blocks", who);
   const int ncomp = ncl + ncf;
 #define TC_GROW(p, cnt)                                            \
   if (int rc = grow(d->p, d->p##_cap, (size_t)(cnt))) return rc
@@ -2096,7 +2185,13 @@ extern "C" int mij_decoder_transcode(mij_decoder *d, int restart_rows) {
   TC_GROW(t_tile, tiles_l + tiles_f);
   TC_GROW(t_rec, ncomp);
   TC_GROW(t_dcjobs, ncomp);
-  TC_GROW(t_abs, nblk);
+  TC_GROW(t_abs, src_nblk);
+  if (xform) {
+    TC_GROW(x_plane, (size_t)nblk * 64);
+    TC_GROW(x_abs, nblk);
+    TC_GROW(x_frames, n);
+    d->h_xframes.assign(n, mij::XfFrame());
+  }
   TC_GROW(t_frames, n);
   TC_GROW(t_outs, n);
   TC_GROW(t_hist, (size_t)n * 4 * 257);
@@ -2119,24 +2214,29 @@ extern "C" int mij_decoder_transcode(mij_decoder *d, int restart_rows) {
   d->h_tdc.assign(ncomp, mij::TcDc());
   d->h_tframes.assign(n, mij::TcFrame());
   int il = 0, ifg = ncl;
-  long long tl = 0, tf = 0, ab = 0, b0 = 0, m0 = 0, r0 = 0;
+  long long tl = 0, tf = 0, ab = 0, xb = 0, b0 = 0, m0 = 0, r0 = 0;
   for (int f = 0; f < n; f++) {
     const Parsed &P = d->parsed[f];
     const FrameLoc &L = d->loc[f];
+    const XfPlan &X = plans[f];
     mij::TcFrame &F = d->h_tframes[f];
     memset(&F, 0, sizeof F);
     F.ncomp = P.ncomp;
-    F.mcus_x = P.mcus_x;
-    F.mcus_y = P.mcus_y;
-    F.R = restart_rows > 0 && restart_rows < P.mcus_y ? restart_rows : P.mcus_y;
-    F.nint = (P.mcus_y + F.R - 1) / F.R;
-    F.ri = restart_rows * P.mcus_x;
+    F.mcus_x = X.mcus_x;
+    F.mcus_y = X.mcus_y;
+    F.R = restart_rows > 0 && restart_rows < X.mcus_y ? restart_rows : X.mcus_y;
+    F.nint = (X.mcus_y + F.R - 1) / F.R;
+    F.ri = restart_rows * X.mcus_x;
     F.blk0 = b0;
     F.mcu0 = (int)m0;
     F.row0 = (int)r0;
     F.rowp0 = (int)r0 + f;
-    F.w = P.w;
-    F.h = P.h;
+    F.w = X.w;
+    F.h = X.h;
+    if (xform) {
+      memset(&d->h_xframes[f], 0, sizeof(mij::XfFrame));
+      d->h_xframes[f].ncomp = P.ncomp;
+    }
     bool used[4] = {false, false, false, false};
     for (int c = 0; c < P.ncomp; c++) {
       const int nb = P.bw[c] * P.bh[c];
@@ -2168,15 +2268,35 @@ extern "C" int mij_decoder_transcode(mij_decoder *d, int restart_rows) {
       mij::TcComp &C = F.c[c];
       C.plane = (L.foreign ? d->f_coef : d->d_coef) + L.off[c];
       C.abs = q.abs;
-      C.hs = P.hs[c];
-      C.vs = P.vs[c];
-      C.bw = P.bw[c];
+      C.hs = X.hs[c];
+      C.vs = X.vs[c];
+      C.bw = X.bw[c];
       ab += nb;
-      F.bpm += P.hs[c] * P.vs[c];
+      if (xform) {  // the stages after k_xf_blocks see its output
+        mij::XfFrame &XF = d->h_xframes[f];
+        mij::XfComp &K = XF.c[c];
+        K.src = C.plane;
+        K.src_abs = q.abs;
+        K.dst = d->x_plane + 64 * xb;
+        K.dst_abs = d->x_abs + xb;
+        K.g.sbw = P.bw[c];
+        K.g.dbw = X.bw[c];
+        K.g.dbh = X.bh[c];
+        K.g.ox = X.ox[c];
+        K.g.oy = X.oy[c];
+        K.g.bits = X.bits;
+        K.blk0 = XF.nblk;
+        XF.nblk += X.bw[c] * X.bh[c];
+        C.plane = K.dst;
+        C.abs = K.dst_abs;
+        xb += (long long)X.bw[c] * X.bh[c];
+      }
+      F.bpm += X.hs[c] * X.vs[c];
       // SOF0's entry verbatim: a lone component keeps the sampling it declared,
-      // which parse() replaced by 1x1 (P.decl_hv)
+      // which parse() replaced by 1x1 (P.decl_hv); X.hv is that byte, its
+      // nibbles swapped by a transposing operation
       F.sof[c][0] = (uint8_t)P.cid[c];
-      F.sof[c][1] = P.decl_hv[c];
+      F.sof[c][1] = X.hv[c];
       F.sof[c][2] = (uint8_t)P.tq[c];
       if (!P.have_dqt[P.tq[c]]) return mij_fail(MIJ_EJPEG, "stream %d: DQT %d of component %d missing", f, P.tq[c], c);
       used[P.tq[c]] = true;
@@ -2184,14 +2304,18 @@ extern "C" int mij_decoder_transcode(mij_decoder *d, int restart_rows) {
     for (int t = 0; t < 4; t++)
       if (used[t]) {  // at most three components: at most three ids
         F.dqt_id[F.ndqt] = (uint8_t)t;
-        memcpy(F.dqt[F.ndqt], P.dqt[t], 64);
+        // (transposed with the blocks)
+        for (int z = 0; z < 64; z++) F.dqt[F.ndqt][z] = P.dqt[t][mij::xf_src_pos(X.bits, z)];
         F.ndqt++;
       }
-    F.nblk = P.mcus_x * P.mcus_y * F.bpm;
+    F.nblk = X.mcus_x * X.mcus_y * F.bpm;
     b0 += F.nblk;
-    m0 += (long long)P.mcus_x * P.mcus_y;
-    r0 += P.mcus_y;
+    m0 += (long long)X.mcus_x * X.mcus_y;
+    r0 += X.mcus_y;
   }
+  if (xform)
+    HIP_TRY(hipMemcpyAsync(d->x_frames, d->h_xframes.data(), n * sizeof(mij::XfFrame), hipMemcpyHostToDevice,
+                           d->stream));
   HIP_TRY(hipMemcpyAsync(d->t_rec, d->h_trec.data(), ncomp * sizeof(mij::IlRec), hipMemcpyHostToDevice, d->stream));
   HIP_TRY(hipMemcpyAsync(d->t_dcjobs, d->h_tdc.data(), ncomp * sizeof(mij::TcDc), hipMemcpyHostToDevice, d->stream));
   HIP_TRY(hipMemcpyAsync(d->t_frames, d->h_tframes.data(), n * sizeof(mij::TcFrame), hipMemcpyHostToDevice,
@@ -2214,6 +2338,7 @@ extern "C" int mij_decoder_transcode(mij_decoder *d, int restart_rows) {
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(mij::launch_tc_abs(d->t_dcjobs, ncomp, max_comp, d->stream));
+  if (xform) HIP_TRY(mij::launch_xf_blocks(d->x_frames, n, max_nblk, d->stream));
   mij::TcArgs a;
   memset(&a, 0, sizeof a);
   a.fr = d->t_frames;
@@ -2284,10 +2409,44 @@ extern "C" int mij_decoder_transcode(mij_decoder *d, int restart_rows) {
   return MIJ_OK;
 }
 
+extern "C" int mij_decoder_transcode(mij_decoder *d, int restart_rows) {
+  mij_clear_error();
+  if (!d) return mij_fail(MIJ_EINVAL, "decoder_transcode: no decoder");
+  if (d->n < 1) return mij_fail(MIJ_EINVAL, "decoder_transcode: no decoded frames");
+  const int n = d->n;
+  for (int f = 0; f < n; f++) {
+    const long long ri = (long long)restart_rows * d->parsed[f].mcus_x;
+    if (restart_rows < 0 || ri > 65535)
+      return mij_fail(MIJ_EINVAL, "decoder_transcode: frame %d: restart interval of %d rows x %d MCUs = %lld MCUs "
+                      "(0..65535)", f, restart_rows, d->parsed[f].mcus_x, ri);
+  }
+  std::vector<XfPlan> plans(n);
+  for (int f = 0; f < n; f++)
+    if (int rc = xf_plan(d->parsed[f], MIJ_XF_NONE, 0, nullptr, restart_rows, "decoder_transcode", f, plans[f]))
+      return rc;
+  return tc_run(d, restart_rows, plans.data(), false, "decoder_transcode");
+}
+
+// mij_decoder_transcode with a transform in front: the same
+// operation, flags and crop for every frame of the last decode; one refused
+// frame refuses the call before any device work.  MIJ_XF_NONE without a crop
+// is the plain transcode.
+extern "C" int mij_decoder_transform(mij_decoder *d, int op, int flags, const area_t *crop, int restart_rows) {
+  mij_clear_error();
+  if (!d) return mij_fail(MIJ_EINVAL, "decoder_transform: no decoder");
+  if (d->n < 1) return mij_fail(MIJ_EINVAL, "decoder_transform: no decoded frames");
+  const int n = d->n;
+  std::vector<XfPlan> plans(n);
+  for (int f = 0; f < n; f++)
+    if (int rc = xf_plan(d->parsed[f], op, flags, crop, restart_rows, "decoder_transform", f, plans[f])) return rc;
+  return tc_run(d, restart_rows, plans.data(), op != MIJ_XF_NONE || crop, "decoder_transform");
+}
+
 // the frame's stream once the last decode has been transcoded
 static int tc_frame(mij_decoder *d, int frame, const char *what) {
   if (!d) return mij_fail(MIJ_EINVAL, "%s: no decoder", what);
-  if (!d->tc_valid) return mij_fail(MIJ_EINVAL, "%s: no mij_decoder_transcode since the last decode", what);
+  if (!d->tc_valid)
+    return mij_fail(MIJ_EINVAL, "%s: no mij_decoder_transcode or mij_decoder_transform since the last decode", what);
   if (frame < 0 || frame >= d->n) return mij_fail(MIJ_EINVAL, "%s: frame %d of %d", what, frame, d->n);
   if (d->tc_err[frame]) return mij_frame_fail(d->tc_err[frame], what, frame);
   return MIJ_OK;
@@ -2318,7 +2477,9 @@ extern "C" void *mij_decoder_device_transcoded(mij_decoder *d, int frame, size_t
 extern "C" int mij_decoder_transcode_ms(mij_decoder *d, float *ms) {
   mij_clear_error();
   if (!d || !ms) return mij_fail(MIJ_EINVAL, "decoder_transcode_ms: bad args");
-  if (!d->tc_valid) return mij_fail(MIJ_EINVAL, "decoder_transcode_ms: no mij_decoder_transcode since the last decode");
+  if (!d->tc_valid)
+    return mij_fail(MIJ_EINVAL, "decoder_transcode_ms: no mij_decoder_transcode or mij_decoder_transform since the "
+                    "last decode");
   HIP_TRY(hipSetDevice(d->dev));
   HIP_TRY(hipEventSynchronize(d->tc_ev[1]));
   HIP_TRY(hipEventElapsedTime(ms, d->tc_ev[0], d->tc_ev[1]));
@@ -2363,4 +2524,78 @@ extern "C" int mij_transcode(const uint8_t *jpg, size_t len, int restart_rows, u
   if (!rc) rc = mij_decoder_transcoded(d, 0, out, cap, out_len);
   decoder_free(d);  // (leaves the failure's message in place)
   return rc;
+}
+
+extern "C" int mij_transform(const uint8_t *jpg, size_t len, int op, int flags, const area_t *crop, int restart_rows,
+                             uint8_t *out, size_t cap, size_t *out_len) {
+  mij_clear_error();
+  if (out_len) *out_len = 0;
+  if (!jpg || (!out && cap)) return mij_fail(MIJ_EINVAL, "mij_transform: NULL buffer");
+  Parsed P;  // the size first: the decoder is made for it; and every refusal, before any device work
+  if (int rc = parse(jpg, len, P, 0)) return mij_fail(rc, "mij_transform: %s", P.err);
+  XfPlan X;
+  if (int rc = xf_plan(P, op, flags, crop, restart_rows, "mij_transform", 0, X)) return rc;
+  mij_decoder *d = mij_decoder_create(mij_drop_device(), (P.w + 15) / 16 * 16, (P.h + 15) / 16 * 16, 1);
+  if (!d) return mij_last_error();
+  int rc = mij_decoder_decode(d, &jpg, &len, 1);
+  if (!rc) rc = mij_decoder_transform(d, op, flags, crop, restart_rows);
+  if (!rc) rc = mij_decoder_transcoded(d, 0, out, cap, out_len);
+  decoder_free(d);  // (leaves the failure's message in place)
+  return rc;
+}
+
+// ---------------------------------------------------------------------------
+// EXIF orientation (host only)
+// ---------------------------------------------------------------------------
+// The segments before SOS: the APP1 that begins "Exif\0\0", its TIFF header
+// (II or MM), IFD0's tag 0x0112 (SHORT).  Every offset is checked against the
+// segment; anything malformed or absent gives 1.
+extern "C" int mij_exif_orientation(const uint8_t *jpg, size_t len) {
+  if (!jpg || len < 4 || jpg[0] != 0xFF || jpg[1] != 0xD8) return 1;
+  size_t i = 2;
+  while (i + 4 <= len) {
+    if (jpg[i] != 0xFF) return 1;
+    const int m = jpg[i + 1];
+    if (m == 0xFF) {  // fill byte
+      i++;
+      continue;
+    }
+    if (m == 0xDA || m == 0xD9) return 1;
+    if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) {  // no length
+      i += 2;
+      continue;
+    }
+    const size_t n = (size_t)be16(jpg + i + 2);
+    if (n < 2 || i + 2 + n > len) return 1;
+    const uint8_t *seg = jpg + i + 4;  // n - 2 bytes
+    i += 2 + n;
+    if (m != 0xE1 || n < 2 + 6 || memcmp(seg, "Exif\0\0", 6)) continue;
+    const uint8_t *t = seg + 6;   // the TIFF header, where offsets count from
+    const size_t tn = n - 2 - 6;  // its bytes inside the segment
+    if (tn < 8) return 1;
+    const bool le = t[0] == 'I' && t[1] == 'I';
+    if (!le && !(t[0] == 'M' && t[1] == 'M')) return 1;
+    auto u16 = [&](size_t o) { return le ? (unsigned)(t[o] | (t[o + 1] << 8)) : (unsigned)((t[o] << 8) | t[o + 1]); };
+    auto u32 = [&](size_t o) { return le ? u16(o) | (u16(o + 2) << 16) : (u16(o) << 16) | u16(o + 2); };
+    if (u16(2) != 42) return 1;
+    const size_t ifd = u32(4);
+    if (ifd > tn || tn - ifd < 2) return 1;
+    const size_t cnt = u16(ifd);
+    for (size_t k = 0; k < cnt; k++) {
+      const size_t e = ifd + 2 + 12 * k;
+      if (e > tn || tn - e < 12) return 1;
+      if (u16(e) != 0x0112) continue;
+      if (u16(e + 2) != 3 || u32(e + 4) != 1) return 1;  // one SHORT, held in the entry
+      const unsigned v = u16(e + 8);
+      return v >= 1 && v <= 8 ? (int)v : 1;
+    }
+    return 1;
+  }
+  return 1;
+}
+
+extern "C" int mij_orientation_op(int orientation) {
+  static const int ops[9] = {MIJ_XF_NONE,      MIJ_XF_NONE,  MIJ_XF_FLIP_H,     MIJ_XF_ROT180, MIJ_XF_FLIP_V,
+                             MIJ_XF_TRANSPOSE, MIJ_XF_ROT90, MIJ_XF_TRANSVERSE, MIJ_XF_ROT270};
+  return orientation >= 1 && orientation <= 8 ? ops[orientation] : MIJ_XF_NONE;
 }

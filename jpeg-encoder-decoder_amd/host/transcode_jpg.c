@@ -9,11 +9,19 @@
  * output as from the input.  APPn / COM segments are not carried over.
  * Entropy decoding and coding both run on the GPU.
  *
- *   transcode_jpg <in.jpg> <out.jpg> [restart_rows]
+ *   transcode_jpg [options] <in.jpg> <out.jpg> [restart_rows]
+ *
+ * With options, the other half of jpegtran, as lossless (mij_decoder_transform):
+ *   -flip h|v  -rotate 90|180|270  -transpose  -transverse
+ *   -auto             the operation that makes the file's EXIF orientation upright
+ *   -crop WxH+X+Y     X and Y multiples of the MCU size
+ *   -trim             cut a mirrored edge down to whole MCUs instead of refusing it
+ * restart_rows then counts MCU rows of the output.
  */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "mijpeg.h"
 
@@ -39,15 +47,46 @@ static int fail(const char *what, int rc) {
     return 1;
 }
 
+static int usage(const char *prog) {
+    fprintf(stderr, "usage: %s [-flip h|v] [-rotate 90|180|270] [-transpose] [-transverse] [-auto] [-trim]\n"
+            "       [-crop WxH+X+Y] <in.jpg> <out.jpg> [restart_rows]\n", prog);
+    return 2;
+}
+
 int main(int argc, char **argv) {
-    if (argc != 3 && argc != 4) {
-        fprintf(stderr, "usage: %s <in.jpg> <out.jpg> [restart_rows]\n", argv[0]);
-        return 2;
+    const char *prog = argv[0];
+    int op = MIJ_XF_NONE, flags = 0, have_crop = 0, have_xf = 0, automatic = 0;
+    area_t crop = {0, 0, 0, 0};
+    while (argc > 1 && argv[1][0] == '-' && argv[1][1]) {
+        const char *o = argv[1], *v = argc > 2 ? argv[2] : "";
+        int used = 1;
+        if (!strcmp(o, "-flip") && (!strcmp(v, "h") || !strcmp(v, "v"))) {
+            op = v[0] == 'h' ? MIJ_XF_FLIP_H : MIJ_XF_FLIP_V, used = 2;
+        } else if (!strcmp(o, "-rotate") && (!strcmp(v, "90") || !strcmp(v, "180") || !strcmp(v, "270"))) {
+            op = !strcmp(v, "90") ? MIJ_XF_ROT90 : !strcmp(v, "180") ? MIJ_XF_ROT180 : MIJ_XF_ROT270, used = 2;
+        } else if (!strcmp(o, "-transpose")) {
+            op = MIJ_XF_TRANSPOSE;
+        } else if (!strcmp(o, "-transverse")) {
+            op = MIJ_XF_TRANSVERSE;
+        } else if (!strcmp(o, "-auto")) {
+            automatic = 1;
+        } else if (!strcmp(o, "-trim")) {
+            flags |= MIJ_XF_TRIM;
+        } else if (!strcmp(o, "-crop") && sscanf(v, "%dx%d+%d+%d", &crop.w, &crop.h, &crop.x, &crop.y) == 4) {
+            have_crop = 1, used = 2;
+        } else {
+            return usage(prog);
+        }
+        have_xf = 1;
+        argc -= used;
+        argv += used;
     }
+    if (argc != 3 && argc != 4) return usage(prog);
     const int restart_rows = argc == 4 ? atoi(argv[3]) : 0;
     size_t len = 0;
     uint8_t *jpg = read_file(argv[1], &len);
     if (!jpg) return 1;
+    if (automatic) op = mij_orientation_op(mij_exif_orientation(jpg, len));
     /* the frame size, for the decoder: mij_decode reports it with MIJ_ENOSPC
      * before any device work */
     int w = 0, h = 0;
@@ -58,7 +97,9 @@ int main(int argc, char **argv) {
     if (!d) return fail("mij_decoder_create", mij_last_error());
     const uint8_t *streams[1] = {jpg};
     if ((rc = mij_decoder_decode(d, streams, &len, 1)) != MIJ_OK) return fail(argv[1], rc);
-    if ((rc = mij_decoder_transcode(d, restart_rows)) != MIJ_OK) return fail(argv[1], rc);
+    rc = have_xf ? mij_decoder_transform(d, op, flags, have_crop ? &crop : NULL, restart_rows)
+                 : mij_decoder_transcode(d, restart_rows);
+    if (rc != MIJ_OK) return fail(argv[1], rc);
     size_t n = 0;
     if (!mij_decoder_device_transcoded(d, 0, &n)) return fail(argv[1], mij_last_error());
     uint8_t *out = malloc(n);

@@ -51,6 +51,7 @@ EXPORTS = [
     "mij_encode_any",
     "mij_decoder_transcode", "mij_decoder_transcoded", "mij_decoder_device_transcoded", "mij_decoder_transcode_ms",
     "mij_transcode",
+    "mij_decoder_transform", "mij_transform", "mij_exif_orientation", "mij_orientation_op",
 ]
 
 
@@ -246,6 +247,10 @@ def load() -> C.CDLL:
         lib.mij_decoder_device_transcoded.argtypes = [p, i, C.POINTER(sz)]
         lib.mij_decoder_transcode_ms.argtypes = [p, C.POINTER(C.c_float)]
         lib.mij_transcode.argtypes = [p, sz, i, p, sz, C.POINTER(sz)]
+        lib.mij_decoder_transform.argtypes = [p, i, i, C.POINTER(Area), i]
+        lib.mij_transform.argtypes = [p, sz, i, i, C.POINTER(Area), i, p, sz, C.POINTER(sz)]
+        lib.mij_exif_orientation.argtypes = [p, sz]
+        lib.mij_orientation_op.argtypes = [i]
     except AttributeError:
         if not os.environ.get("MIJ_LIB"):  # older builds only in A/B timing runs
             raise
@@ -973,6 +978,57 @@ def transcode(jpg: bytes, restart_rows: int = 0) -> bytes:
     return out[:n.value].tobytes()
 
 
+# MIJ_XF_*: jpegtran's JXFORM order; rot90 is clockwise
+XF_OPS = {"none": 0, "flip_h": 1, "flip_v": 2, "transpose": 3, "transverse": 4, "rot90": 5, "rot180": 6, "rot270": 7}
+XF_TRIM = 1
+
+
+def exif_orientation(jpg: bytes) -> int:
+    """mij_exif_orientation: 1..8, 1 where the stream has no (well-formed) EXIF orientation; host only"""
+    buf = np.frombuffer(jpg, np.uint8)
+    return load().mij_exif_orientation(_ptr(buf), buf.size)
+
+
+def orientation_op(n: int) -> str:
+    """the operation (by name) that makes an image of EXIF orientation n upright"""
+    code = load().mij_orientation_op(n)
+    return next(k for k, v in XF_OPS.items() if v == code)
+
+
+def _xf_args(jpg, op, trim, crop):
+    """(op code, flags, crop pointer or None) of a transform call"""
+    if op == "auto":
+        if jpg is None:
+            raise MijError("op 'auto' needs the stream: transform(jpg, 'auto'), or "
+                           "orientation_op(exif_orientation(jpg))")
+        op = orientation_op(exif_orientation(jpg))
+    if isinstance(op, str):
+        if op not in XF_OPS:
+            raise MijError(f"operation {op!r}: one of {', '.join(XF_OPS)} or 'auto'")
+        op = XF_OPS[op]
+    area = C.byref(Area(*[int(v) for v in crop])) if crop is not None else None
+    return int(op), XF_TRIM if trim is True else int(trim), area
+
+
+def transform(jpg: bytes, op="rot90", trim: bool = False, crop=None, restart_rows: int = 0) -> bytes:
+    """mij_transform: one baseline stream -> the flipped / transposed / rotated
+    (op, by name; "auto": by the stream's EXIF orientation) and / or cropped
+    (crop = (x, y, w, h), MCU-aligned offset) image, coded as transcode codes
+    it; lossless.  trim: cut a mirrored dimension down to
+    whole MCUs instead of refusing it."""
+    lib = load()
+    buf = np.frombuffer(jpg, np.uint8)
+    code, flags, area = _xf_args(jpg, op, trim, crop)
+    n = C.c_size_t(0)
+    out = np.zeros(len(jpg) + 4096, np.uint8)  # enough for most; the exact size comes back otherwise
+    rc = lib.mij_transform(_ptr(buf), buf.size, code, flags, area, restart_rows, _ptr(out), out.nbytes, C.byref(n))
+    if rc == 4 and n.value > out.nbytes:  # MIJ_ENOSPC
+        out = np.zeros(n.value, np.uint8)
+        rc = lib.mij_transform(_ptr(buf), buf.size, code, flags, area, restart_rows, _ptr(out), out.nbytes, C.byref(n))
+    _check(rc, "mij_transform")
+    return out[:n.value].tobytes()
+
+
 class Decoder:
     """Baseline JPEG streams (the encoder's own three-scan shape, and what
     libjpeg writes: one interleaved scan, greyscale / 4:4:4 / 4:2:2 / 4:2:0,
@@ -1096,8 +1152,15 @@ class Decoder:
         stream (mij_decoder_transcode); waits for the device"""
         _check(self.lib.mij_decoder_transcode(self.h_, restart_rows), "decoder_transcode")
 
+    def transform(self, op="rot90", trim: bool = False, crop=None, restart_rows: int = 0) -> None:
+        """every frame of the last decode -> its transformed and / or cropped
+        image, coded as transcode codes it (mij_decoder_transform; op by
+        name); read with transcoded / device_transcoded / transcode_ms"""
+        code, flags, area = _xf_args(None, op, trim, crop)
+        _check(self.lib.mij_decoder_transform(self.h_, code, flags, area, restart_rows), "decoder_transform")
+
     def transcoded(self, frame: int) -> bytes:
-        """host copy of `frame`'s stream of the last transcode"""
+        """host copy of `frame`'s stream of the last transcode or transform"""
         _, size = self.device_transcoded(frame)
         n = C.c_size_t(0)
         out = np.zeros(size, np.uint8)
