@@ -606,6 +606,36 @@ void *mij_decoder_stream(mij_decoder *d);
  * decode, MIJ_ENOSPC for a short cap (everywhere above) */
 int mij_decode(const uint8_t *jpg, size_t len, int order, uint8_t *out, size_t cap, int *w, int *h);
 
+/* ---- decode at 1/2, 1/4, 1/8 scale ---------------------------
+ * What djpeg -scale 1/N and Pillow's Image.draft give: libjpeg's reduced
+ * IDCTs make 4x4, 2x2 or 1x1 samples of every block (4:2:0 chroma twice that,
+ * so it needs no upsampling), and the pixels are libjpeg's byte for byte.  The
+ * output is ceil(w * s / 8) x ceil(h * s / 8) with s = 8 / denom.
+ *
+ * mij_decoder_reconstruct_scaled: as mij_decoder_reconstruct, at 1/denom;
+ * denom 1 IS mij_decoder_reconstruct, 2, 4, 8 as above, anything else
+ * MIJ_EINVAL before any device work.  Afterwards mij_decoder_pixels,
+ * _device_pixels (pitch: 3 * scaled width rounded up to 16) and
+ * _reconstruct_ms serve the scaled result, mij_decoder_plane gives the
+ * component's scaled padded plane (mij_decoder_scaled_layout: rows x pitch
+ * bytes; the bytes of a row past S * blocks across are 0), and
+ * mij_decoder_planes returns MIJ_EINVAL.  A later reconstruct of either
+ * kind replaces the result; transcode and transform are not affected. */
+int mij_decoder_reconstruct_scaled(mij_decoder *d, int order, int denom);
+/* host only, valid after a decode, denom 1, 2, 4 or 8 (else MIJ_EINVAL):
+ * out[0..2] = scaled width, scaled height,
+ * components; then per component the IDCT's output size S (S x S samples per
+ * block), the component's real width and height in samples, the bytes
+ * between rows of its padded plane and that plane's rows.  MIJ_ENOSPC if
+ * n < 3 + 5 * components (at most 18) */
+#define MIJ_SCALED_LAYOUT_MAX 18
+int mij_decoder_scaled_layout(mij_decoder *d, int frame, int denom, int *out, int n);
+/* mirror of mij_decode at 1/denom: *w and *h receive the SCALED size as soon
+ * as the headers are read, also with MIJ_ENOSPC (cap 0 asks for the size
+ * without a device) */
+int mij_decode_scaled(const uint8_t *jpg, size_t len, int order, int denom, uint8_t *out, size_t cap, int *w,
+                      int *h);
+
 /* ---- lossless transcoding ------------------------------------
  * What jpegtran -optimize does, on the GPU: every frame of the last decode,
  * of either kind above, becomes one standard interleaved baseline stream

@@ -896,6 +896,130 @@ __global__ __launch_bounds__(256) void k_il_colour(const IlPix *frames, int nfra
   colour_tile_any(planes + fr.y, planes + fr.cb, planes + fr.cr, fr.G, u, g, rgb, pix + fr.pix);
 }
 
+// ---------------------------------------------------------------------------
+// Decoding at 1/2, 1/4 and 1/8 scale.  The absolute DCs come
+// from the kernels above, unchanged; a component whose blocks become S x S
+// samples (mij_pixels.h scaled_geometry) goes through k_sc_idct<S> into a
+// plane whose rows are S * bw rounded up to 8 bytes apart, at the place its
+// full-size plane would take; k_il_colour then runs on the scaled geometry.
+// Frames of the encoder's own shape take the same path as any 4:2:0 frame.
+//
+// Bounds.  A lane owns strip t < bh * spr of its component: block row by =
+// t / spr, blocks bx0 = (8 / S) * sx .. of which only those < bw are read.
+// Its S stores of 8 bytes go to rows S * by .. S * by + S - 1 < S * bh at
+// byte 8 * sx, and 8 * sx + 8 <= 8 * spr == pitch, so each stays inside its
+// row of the plane, which is pitch * S * bh <= 64 * bw * bh bytes: inside the
+// slot of the full-size plane.  In LDS a workgroup's block b < nb <= 256
+// has its staging slot at 9 * b int4 and its rows at words 256 * r + b,
+// r < S <= 4: both inside the 256 * 9 int4.  Nothing is addressed from data.
+// ---------------------------------------------------------------------------
+struct ScJob {      // one component of one frame
+  long long off;    // as RecJob
+  int nblocks, bw, bh;
+  int wg0, qt, tile0;
+  int hs, vs, mcus_x, seg;  // as IlRec (il only)
+  int il;           // the DC rule: 1 = k_il_idct's (scan order, segments), 0 = k_dec_idct's (raster)
+  int pitch;        // bytes between the scaled plane's rows
+  int spr;          // strips of 8 samples per block row: ceil(bw * S / 8)
+  int pad;
+};
+
+__device__ __forceinline__ uint32_t sc_dc(const ScJob &j, const int32_t *pd, const uint32_t *tile, int blk) {
+  if (!j.il) return (uint32_t)pd[blk] + tile[j.tile0 + blk / DC_TILE];
+  const int by = blk / j.bw, bx = blk - by * j.bw;
+  const int my = by / j.vs, iy = by - my * j.vs, mx = bx / j.hs, ix = bx - mx * j.hs;
+  const int s = (my * j.mcus_x + mx) * (j.hs * j.vs) + iy * j.hs + ix, s0 = s / j.seg * j.seg;
+  uint32_t v = (uint32_t)pd[s] + tile[j.tile0 + s / DC_TILE];
+  if (s0 > 0) v -= (uint32_t)pd[s0 - 1] + tile[j.tile0 + (s0 - 1) / DC_TILE];
+  return v;
+}
+
+// One lane stores a strip: the 8 / S horizontally adjacent blocks of one
+// block row that make 8 output samples, so every row leaves as one aligned
+// 8-byte store.  A workgroup takes 256 * S / 8 consecutive strips, i.e. at
+// most 256 blocks, consecutive in raster order also where a block row ends
+// in a partial strip; all 256 lanes stage their coefficients through LDS as
+// k_il_idct does.  For S == 4 and 2 every lane then runs the IDCT of one
+// block (so none idles), leaves its S rows in LDS, in the staging area once
+// every lane has read its coefficients, and the strip lanes gather them.
+// S == 8 is k_il_idct itself with the job's DC rule (4:2:0 chroma at 1/2);
+// S == 1 reads the DC buffers alone, 8 blocks per lane.
+template <int S>
+__global__ __launch_bounds__(256) void k_sc_idct(const ScJob *jobs, int njobs, const int16_t *coefs, const int32_t *dc,
+                                                 const uint32_t *tile, const int32_t *q, uint8_t *planes) {
+  constexpr int PER = 8 / S, LANES = 256 / PER;
+  __shared__ int4 stage[S > 1 ? 256 * 9 : 1];
+  const ScJob job = jobs[rec_job_of(jobs, njobs, blockIdx.x)];
+  const int nstrips = job.bh * job.spr;
+  const int t0 = ((int)blockIdx.x - job.wg0) * LANES, t1 = min(t0 + LANES, nstrips);
+  const int by0 = t0 / job.spr, first = by0 * job.bw + (t0 - by0 * job.spr) * PER;
+  const int32_t *pd = dc + job.off / 64;
+  const int32_t *qz = q + 64 * job.qt;
+  int nb = 0;  // the workgroup's blocks: <= 256
+  if (S > 1) {
+    const int by1 = t1 / job.spr, last = t1 == nstrips ? job.nblocks : by1 * job.bw + (t1 - by1 * job.spr) * PER;
+    nb = last - first;
+    const int4 *src = (const int4 *)(coefs + job.off + 64LL * first);
+    for (int i = threadIdx.x; i < nb * 8; i += 256) stage[(i >> 3) * 9 + (i & 7)] = src[i];
+    __syncthreads();
+  }
+  uint32_t *res = (uint32_t *)stage;  // S == 4, 2: row r of the workgroup's block b at res[256 * r + b]
+  if constexpr (S == 4 || S == 2) {
+    uint32_t rows[S];
+    const bool have = (int)threadIdx.x < nb;
+    if (have) {
+      union {
+        int4 v[8];
+        int16_t c[64];
+      } in;
+#pragma unroll
+      for (int j = 0; j < 8; j++) in.v[j] = stage[threadIdx.x * 9 + j];
+      const uint32_t dc_abs = sc_dc(job, pd, tile, first + (int)threadIdx.x);
+      if constexpr (S == 4) idct4_block(in.c, dc_abs, qz, rows);
+      else idct2_block(in.c, dc_abs, qz, rows);
+    }
+    __syncthreads();  // every lane holds its coefficients in registers: the staging area is free
+    if (have) {
+#pragma unroll
+      for (int r = 0; r < S; r++) res[256 * r + threadIdx.x] = rows[r];
+    }
+    __syncthreads();
+  }
+  const int t = t0 + (int)threadIdx.x;
+  if ((int)threadIdx.x >= LANES || t >= t1) return;
+  const int by = t / job.spr, sx = t - by * job.spr;
+  const int blk0 = by * job.bw + sx * PER, nbl = min(PER, job.bw - sx * PER);
+  uint32_t out[S][2];
+#pragma unroll
+  for (int r = 0; r < S; r++) out[r][0] = out[r][1] = 0;
+#pragma unroll
+  for (int k = 0; k < PER; k++) {
+    if (k >= nbl) break;
+    const int blk = blk0 + k;
+    if constexpr (S == 1) {
+      out[0][k >> 2] |= idct1_block(sc_dc(job, pd, tile, blk), qz[0]) << (8 * (k & 3));
+    } else if constexpr (S == 8) {
+      union {
+        int4 v[8];
+        int16_t c[64];
+      } in;
+#pragma unroll
+      for (int j = 0; j < 8; j++) in.v[j] = stage[(blk - first) * 9 + j];
+      idct_block(in.c, sc_dc(job, pd, tile, blk), qz, out);
+    } else if constexpr (S == 4) {
+#pragma unroll
+      for (int r = 0; r < 4; r++) out[r][k] = res[256 * r + blk - first];
+    } else {
+#pragma unroll
+      for (int r = 0; r < 2; r++) out[r][k >> 1] |= res[256 * r + blk - first] << (16 * (k & 1));
+    }
+  }
+  uint8_t *dst = planes + job.off + (long long)S * by * job.pitch + 8 * sx;
+#pragma unroll
+  for (int r = 0; r < S; r++)  // 8-byte aligned: off % 64 == 0, pitch % 8 == 0
+    store_as(dst + (long long)r * job.pitch, W2{out[r][0], out[r][1]});
+}
+
 }  // namespace mij
 
 // ---------------------------------------------------------------------------
@@ -1233,6 +1357,16 @@ struct mij_decoder {
   std::vector<mij::IlRec> h_irec;
   std::vector<mij::IlPix> h_ipix;
   std::vector<int32_t> h_irecq;
+  // decoding at 1/2, 1/4, 1/8 scale (mij_decoder_reconstruct_scaled, DESIGN.md
+  // §4j): the job tables only; planes and pixels take the places of the
+  // full-size ones
+  int rec_denom = 1;  // of the last reconstruct
+  std::vector<mij::ScaledGeom> sgeom;  // per frame, when rec_denom > 1
+  mij::ScJob *s_jobs = nullptr;
+  mij::IlPix *s_pix = nullptr;
+  size_t s_jobs_cap = 0, s_pix_cap = 0;
+  std::vector<mij::ScJob> h_sjobs;
+  std::vector<mij::IlPix> h_spix;
   // lossless transcoding (mij_decoder_transcode): everything allocated at its
   // first call and grown like the arena.  It keeps its own DC prefix sums, so
   // that it and reconstruct may run in either order, or alone.
@@ -1305,6 +1439,8 @@ static void decoder_free(mij_decoder *d) {
   hipFree(d->f_status);
   hipFree(d->f_rjobs);
   hipFree(d->f_rpix);
+  hipFree(d->s_jobs);
+  hipFree(d->s_pix);
   for (void *p : {(void *)d->t_dcl, (void *)d->t_dcf, (void *)d->t_tile, (void *)d->t_rec, (void *)d->t_dcjobs,
                   (void *)d->t_abs, (void *)d->t_frames, (void *)d->t_outs, (void *)d->t_hist, (void *)d->t_ehuf,
                   (void *)d->t_hc, (void *)d->t_blk_bits, (void *)d->t_mcu_off, (void *)d->t_row_bits,
@@ -1812,11 +1948,16 @@ static int pix_mode(const Parsed &P) {
   return rep ? mij::PIX_H2V2_REP : mij::PIX_H2V2;
 }
 
-extern "C" int mij_decoder_reconstruct(mij_decoder *d, int order) {
+static int reconstruct_scaled_launch(mij_decoder *d, int order, int denom);
+
+// denom 1: full size; 2, 4, 8: DESIGN.md §4j
+static int reconstruct_any(mij_decoder *d, int order, int denom) {
   mij_clear_error();
   if (!d) return mij_fail(MIJ_EINVAL, "decoder_reconstruct: no decoder");
   if (order != MIJ_PIX_BGR && order != MIJ_PIX_RGB)
     return mij_fail(MIJ_EINVAL, "decoder_reconstruct: pixel order %d", order);
+  if (denom != 1 && denom != 2 && denom != 4 && denom != 8)
+    return mij_fail(MIJ_EINVAL, "decoder_reconstruct_scaled: scale 1/%d: 1/1, 1/2, 1/4 or 1/8", denom);
   if (d->n < 1) return mij_fail(MIJ_EINVAL, "decoder_reconstruct: no decoded frames");
   HIP_TRY(hipSetDevice(d->dev));
   const int n = d->n;
@@ -1933,6 +2074,13 @@ extern "C" int mij_decoder_reconstruct(mij_decoder *d, int order) {
     HIP_TRY(hipMemcpyAsync(d->d_recq, d->h_recq.data(), d->h_recq.size() * sizeof(int32_t), hipMemcpyHostToDevice,
                            d->stream));
   }
+  const int nir = (int)d->h_irec.size();
+  if (denom > 1) {  // the same DC kernels, then the scaled IDCTs and the colour stage on the scaled geometry
+    if (int rc = reconstruct_scaled_launch(d, order, denom)) return rc;
+    d->rec_denom = denom;
+    d->rec_valid = true;
+    return MIJ_OK;
+  }
   HIP_TRY(hipEventRecord(d->rec_ev[0], d->stream));
   if (nl) {
     hipLaunchKernelGGL(mij::k_dec_dc, dim3((unsigned)tiles), dim3(mij::DC_T), 0, d->stream, d->d_rjobs, 3 * nl,
@@ -1942,7 +2090,6 @@ extern "C" int mij_decoder_reconstruct(mij_decoder *d, int order) {
     hipLaunchKernelGGL(mij::k_dec_idct, dim3((unsigned)idct_wgs), dim3(256), 0, d->stream, d->d_rjobs, 3 * nl,
                        d->d_coef, d->d_dc, d->d_tile, d->d_recq, d->d_planes);
   }
-  const int nir = (int)d->h_irec.size();
   if (nf) {
     hipLaunchKernelGGL(mij::k_il_dc, dim3((unsigned)i_tiles), dim3(mij::DC_T), 0, d->stream, d->f_rjobs, nir,
                        d->f_coef, d->f_dc, d->f_tile);
@@ -1961,7 +2108,169 @@ extern "C" int mij_decoder_reconstruct(mij_decoder *d, int order) {
                        d->f_pix, order == MIJ_PIX_RGB);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(d->rec_ev[2], d->stream));
+  d->rec_denom = 1;
   d->rec_valid = true;
+  return MIJ_OK;
+}
+
+static void scaled_geom(const Parsed &P, int denom, mij::ScaledGeom &G) {
+  mij::scaled_geometry(P.w, P.h, P.ncomp, P.hs, P.vs, P.bw, P.bh, denom, G);
+}
+
+// reconstruct_any's second half at 1/2, 1/4, 1/8: d->h_rjobs / h_irec are
+// built and on their way to the device, the buffers exist
+static int reconstruct_scaled_launch(mij_decoder *d, int order, int denom) {
+  const int n = d->n;
+  d->sgeom.resize(n);
+  // ScJobs in eight runs: legacy frames' then the arena's, each by IDCT size 8, 4, 2, 1
+  std::vector<mij::ScJob> run[2][4];
+  long long wgs[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, col[2] = {0, 0};
+  std::vector<mij::IlPix> pix[2];
+  int li = 0, ir = 0;
+  for (int f = 0; f < n; f++) {
+    const Parsed &P = d->parsed[f];
+    const FrameLoc &L = d->loc[f];
+    mij::ScaledGeom &G = d->sgeom[f];
+    scaled_geom(P, denom, G);
+    const int set = L.foreign ? 1 : 0;
+    for (int c = 0; c < P.ncomp; c++) {
+      mij::ScJob j;
+      memset(&j, 0, sizeof j);
+      j.off = L.off[c];
+      j.bw = P.bw[c];
+      j.bh = P.bh[c];
+      j.nblocks = P.bw[c] * P.bh[c];
+      if (L.foreign) {
+        const mij::IlRec &r = d->h_irec[ir++];
+        j.qt = r.qt;
+        j.tile0 = r.tile0;
+        j.hs = r.hs;
+        j.vs = r.vs;
+        j.mcus_x = r.mcus_x;
+        j.seg = r.seg;
+        j.il = 1;
+      } else {
+        const mij::RecJob &r = d->h_rjobs[3 * li + c];
+        j.qt = r.qt;
+        j.tile0 = r.tile0;
+        j.hs = j.vs = j.mcus_x = j.seg = 1;
+      }
+      const int S = G.c[c].S, k = S == 8 ? 0 : S == 4 ? 1 : S == 2 ? 2 : 3;
+      j.pitch = G.c[c].pitch;
+      j.spr = G.c[c].pitch / 8;
+      j.wg0 = (int)wgs[set][k];
+      wgs[set][k] += ((long long)j.bh * j.spr + 32 * S - 1) / (32 * S);  // 256 * S / 8 strips per workgroup
+      run[set][k].push_back(j);
+    }
+    if (!L.foreign) li++;
+    mij::IlPix px;
+    memset(&px, 0, sizeof px);
+    px.y = L.off[0];
+    px.cb = L.off[P.ncomp > 1 ? 1 : 0];
+    px.cr = L.off[P.ncomp > 1 ? 2 : 0];
+    px.pix = L.pix;
+    px.G.w = G.ow;
+    px.G.h = G.oh;
+    px.G.mode = G.mode;
+    px.G.yp = G.c[0].pitch;
+    px.G.cp = G.c[1].pitch;
+    px.G.cw = G.c[1].cw;
+    px.G.ch = G.c[1].ch;
+    px.G.pitch = (3LL * G.ow + 15) / 16 * 16;
+    px.groups = (G.ow + 15) / 16;
+    const int rows = mij::pix_rows_per_lane(G.mode);
+    px.units = (G.oh + rows - 1) / rows;
+    px.wg0 = (int)col[set];
+    col[set] += ((long long)px.units * px.groups + 255) / 256;
+    pix[set].push_back(px);
+  }
+  d->h_sjobs.clear();
+  d->h_spix.clear();
+  size_t first[2][4], pfirst[2];
+  for (int set = 0; set < 2; set++) {
+    for (int k = 0; k < 4; k++) {
+      if (wgs[set][k] > 0x7fffffff) return mij_fail(MIJ_EINVAL, "decoder_reconstruct_scaled: too many blocks");
+      first[set][k] = d->h_sjobs.size();
+      d->h_sjobs.insert(d->h_sjobs.end(), run[set][k].begin(), run[set][k].end());
+    }
+    if (col[set] > 0x7fffffff) return mij_fail(MIJ_EINVAL, "decoder_reconstruct_scaled: too many blocks");
+    pfirst[set] = d->h_spix.size();
+    d->h_spix.insert(d->h_spix.end(), pix[set].begin(), pix[set].end());
+  }
+  if (int rc = grow(d->s_jobs, d->s_jobs_cap, d->h_sjobs.size())) return rc;
+  if (int rc = grow(d->s_pix, d->s_pix_cap, d->h_spix.size())) return rc;
+  HIP_TRY(hipMemcpyAsync(d->s_jobs, d->h_sjobs.data(), d->h_sjobs.size() * sizeof(mij::ScJob), hipMemcpyHostToDevice,
+                         d->stream));
+  HIP_TRY(hipMemcpyAsync(d->s_pix, d->h_spix.data(), d->h_spix.size() * sizeof(mij::IlPix), hipMemcpyHostToDevice,
+                         d->stream));
+  HIP_TRY(hipEventRecord(d->rec_ev[0], d->stream));
+  const int nl = (int)pix[0].size(), nf = (int)pix[1].size(), nir = (int)d->h_irec.size();
+  if (nl) {
+    const mij::RecJob &last = d->h_rjobs.back();
+    const int tiles = last.tile0 + (last.nblocks + mij::DC_TILE - 1) / mij::DC_TILE;
+    hipLaunchKernelGGL(mij::k_dec_dc, dim3((unsigned)tiles), dim3(mij::DC_T), 0, d->stream, d->d_rjobs, 3 * nl,
+                       d->d_coef, d->d_dc, d->d_tile);
+    hipLaunchKernelGGL(mij::k_dec_dcbase<mij::RecJob>, dim3((3 * nl + 63) / 64), dim3(64), 0, d->stream, d->d_rjobs,
+                       3 * nl, d->d_tile);
+  }
+  if (nf) {
+    const mij::IlRec &last = d->h_irec.back();
+    const int tiles = last.tile0 + (last.nblocks + mij::DC_TILE - 1) / mij::DC_TILE;
+    hipLaunchKernelGGL(mij::k_il_dc, dim3((unsigned)tiles), dim3(mij::DC_T), 0, d->stream, d->f_rjobs, nir, d->f_coef,
+                       d->f_dc, d->f_tile);
+    hipLaunchKernelGGL(mij::k_dec_dcbase<mij::IlRec>, dim3((nir + 63) / 64), dim3(64), 0, d->stream, d->f_rjobs, nir,
+                       d->f_tile);
+  }
+  for (int set = 0; set < 2; set++) {
+    const int16_t *coefs = set ? d->f_coef : d->d_coef;
+    const int32_t *dc = set ? d->f_dc : d->d_dc, *q = set ? d->f_recq : d->d_recq;
+    const uint32_t *tile = set ? d->f_tile : d->d_tile;
+    uint8_t *planes = set ? d->f_planes : d->d_planes;
+#define SC_LAUNCH(S, k)                                                                                           \
+  if (wgs[set][k])                                                                                                \
+    hipLaunchKernelGGL(mij::k_sc_idct<S>, dim3((unsigned)wgs[set][k]), dim3(256), 0, d->stream,                   \
+                       d->s_jobs + first[set][k], (int)run[set][k].size(), coefs, dc, tile, q, planes)
+    SC_LAUNCH(8, 0);
+    SC_LAUNCH(4, 1);
+    SC_LAUNCH(2, 2);
+    SC_LAUNCH(1, 3);
+#undef SC_LAUNCH
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(d->rec_ev[1], d->stream));
+  for (int set = 0; set < 2; set++)
+    if (col[set])
+      hipLaunchKernelGGL(mij::k_il_colour, dim3((unsigned)col[set]), dim3(256), 0, d->stream, d->s_pix + pfirst[set],
+                         (int)pix[set].size(), set ? d->f_planes : d->d_planes, set ? d->f_pix : d->d_pix,
+                         order == MIJ_PIX_RGB);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(d->rec_ev[2], d->stream));
+  return MIJ_OK;
+}
+
+extern "C" int mij_decoder_reconstruct(mij_decoder *d, int order) { return reconstruct_any(d, order, 1); }
+
+extern "C" int mij_decoder_reconstruct_scaled(mij_decoder *d, int order, int denom) {
+  return reconstruct_any(d, order, denom);
+}
+
+extern "C" int mij_decoder_scaled_layout(mij_decoder *d, int frame, int denom, int *out, int n) {
+  mij_clear_error();
+  if (!d || frame < 0 || frame >= d->n || !out) return mij_fail(MIJ_EINVAL, "decoder_scaled_layout: bad args");
+  if (denom != 1 && denom != 2 && denom != 4 && denom != 8)
+    return mij_fail(MIJ_EINVAL, "decoder_scaled_layout: scale 1/%d: 1/1, 1/2, 1/4 or 1/8", denom);
+  const Parsed &P = d->parsed[frame];
+  const int need = 3 + 5 * P.ncomp;
+  if (n < need) return mij_fail(MIJ_ENOSPC, "decoder_scaled_layout: need %d ints", need);
+  mij::ScaledGeom G;
+  scaled_geom(P, denom, G);
+  out[0] = G.ow;
+  out[1] = G.oh;
+  out[2] = P.ncomp;
+  for (int c = 0; c < P.ncomp; c++) {
+    const int e[5] = {G.c[c].S, G.c[c].cw, G.c[c].ch, G.c[c].pitch, G.c[c].rows};
+    memcpy(out + 3 + 5 * c, e, sizeof e);
+  }
   return MIJ_OK;
 }
 
@@ -1974,21 +2283,38 @@ static int rec_frame(mij_decoder *d, int frame, const char *what, const Parsed *
   return MIJ_OK;
 }
 
+// size and device pitch of the frame's pixels as the last reconstruct left them
+static void rec_size(const mij_decoder *d, int frame, int *w, int *h, long long *pitch) {
+  const Parsed &P = d->parsed[frame];
+  if (d->rec_denom > 1) {
+    *w = d->sgeom[frame].ow;
+    *h = d->sgeom[frame].oh;
+    *pitch = (3LL * *w + 15) / 16 * 16;
+  } else {
+    *w = P.w;
+    *h = P.h;
+    *pitch = d->loc[frame].foreign ? P.pitch() : 3LL * P.w;  // legacy widths: 3 * w is a multiple of 16 already
+  }
+}
+
 extern "C" int mij_decoder_pixels(mij_decoder *d, int frame, uint8_t *dst, size_t cap, long long pitch) {
   mij_clear_error();
   const Parsed *P;
   if (int rc = rec_frame(d, frame, "decoder_pixels", &P)) return rc;
   if (!dst) return mij_fail(MIJ_EINVAL, "decoder_pixels: dst is NULL");
-  const long long row = 3LL * P->w;
+  int w, h;
+  long long dpitch;
+  rec_size(d, frame, &w, &h, &dpitch);
+  const long long row = 3LL * w;
   if (pitch == 0) pitch = row;
   if (pitch < row) return mij_fail(MIJ_EINVAL, "decoder_pixels: pitch %lld < %lld", pitch, row);
-  const unsigned long long need = (unsigned long long)(P->h - 1) * pitch + row;
+  const unsigned long long need = (unsigned long long)(h - 1) * pitch + row;
   if (cap < need) return mij_fail(MIJ_ENOSPC, "decoder_pixels: need %llu bytes", need);
   HIP_TRY(hipSetDevice(d->dev));
   const FrameLoc &L = d->loc[frame];
   const uint8_t *src = (L.foreign ? d->f_pix : d->d_pix) + L.pix;
-  HIP_TRY(hipMemcpy2DAsync(dst, (size_t)pitch, src, (size_t)(L.foreign ? P->pitch() : row), (size_t)row, P->h,
-                           hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipMemcpy2DAsync(dst, (size_t)pitch, src, (size_t)dpitch, (size_t)row, h, hipMemcpyDeviceToHost,
+                           d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
   return MIJ_OK;
 }
@@ -1998,6 +2324,9 @@ extern "C" int mij_decoder_planes(mij_decoder *d, int frame, uint8_t *Y, uint8_t
   const Parsed *P;
   if (int rc = rec_frame(d, frame, "decoder_planes", &P)) return rc;
   if (!Y || !Cb || !Cr) return mij_fail(MIJ_EINVAL, "decoder_planes: NULL plane");
+  if (d->rec_denom > 1)
+    return mij_fail(MIJ_EINVAL, "decoder_planes: the last reconstruct was at 1/%d scale; use mij_decoder_scaled_layout "
+                    "and mij_decoder_plane", d->rec_denom);
   if (d->loc[frame].foreign)
     return mij_fail(MIJ_EINVAL, "decoder_planes: frame %d is not of the encoder's layout; use mij_decoder_layout and "
                     "mij_decoder_plane", frame);
@@ -2017,7 +2346,8 @@ extern "C" int mij_decoder_plane(mij_decoder *d, int frame, int comp, uint8_t *d
   if (int rc = rec_frame(d, frame, "decoder_plane", &P)) return rc;
   if (!dst) return mij_fail(MIJ_EINVAL, "decoder_plane: dst is NULL");
   if (comp < 0 || comp >= P->ncomp) return mij_fail(MIJ_EINVAL, "decoder_plane: component %d of %d", comp, P->ncomp);
-  const size_t nbytes = (size_t)64 * P->bw[comp] * P->bh[comp];
+  size_t nbytes = (size_t)64 * P->bw[comp] * P->bh[comp];
+  if (d->rec_denom > 1) nbytes = (size_t)d->sgeom[frame].c[comp].pitch * d->sgeom[frame].c[comp].rows;
   if (cap < nbytes) return mij_fail(MIJ_ENOSPC, "decoder_plane: need %zu bytes", nbytes);
   HIP_TRY(hipSetDevice(d->dev));
   const FrameLoc &L = d->loc[frame];
@@ -2032,7 +2362,10 @@ extern "C" void *mij_decoder_device_pixels(mij_decoder *d, int frame, long long 
   const Parsed *P;
   if (rec_frame(d, frame, "decoder_device_pixels", &P)) return nullptr;
   const FrameLoc &L = d->loc[frame];
-  if (pitch) *pitch = L.foreign ? P->pitch() : 3LL * P->w;  // legacy widths: 3 * w is a multiple of 16 already
+  int w, h;
+  long long dpitch;
+  rec_size(d, frame, &w, &h, &dpitch);
+  if (pitch) *pitch = dpitch;
   return (L.foreign ? d->f_pix : d->d_pix) + L.pix;
 }
 
@@ -2502,6 +2835,32 @@ extern "C" int mij_decode(const uint8_t *jpg, size_t len, int order, uint8_t *ou
   if (!d) return mij_last_error();
   int rc = mij_decoder_decode(d, &jpg, &len, 1);
   if (!rc) rc = mij_decoder_reconstruct(d, order);
+  if (!rc) rc = mij_decoder_pixels(d, 0, out, cap, 0);
+  decoder_free(d);  // (leaves the failure's message in place)
+  return rc;
+}
+
+extern "C" int mij_decode_scaled(const uint8_t *jpg, size_t len, int order, int denom, uint8_t *out, size_t cap,
+                                 int *w, int *h) {
+  if (denom == 1) return mij_decode(jpg, len, order, out, cap, w, h);
+  mij_clear_error();
+  if (!jpg || !out) return mij_fail(MIJ_EINVAL, "mij_decode_scaled: NULL buffer");
+  if (order != MIJ_PIX_BGR && order != MIJ_PIX_RGB)
+    return mij_fail(MIJ_EINVAL, "mij_decode_scaled: pixel order %d", order);
+  if (denom != 2 && denom != 4 && denom != 8)
+    return mij_fail(MIJ_EINVAL, "mij_decode_scaled: scale 1/%d: 1/1, 1/2, 1/4 or 1/8", denom);
+  Parsed P;
+  if (int rc = parse(jpg, len, P, 0)) return mij_fail(rc, "mij_decode_scaled: %s", P.err);
+  mij::ScaledGeom G;
+  scaled_geom(P, denom, G);
+  if (w) *w = G.ow;
+  if (h) *h = G.oh;
+  const unsigned long long need = 3ULL * G.ow * G.oh;
+  if (cap < need) return mij_fail(MIJ_ENOSPC, "mij_decode_scaled: need %llu bytes", need);
+  mij_decoder *d = mij_decoder_create(mij_drop_device(), (P.w + 15) / 16 * 16, (P.h + 15) / 16 * 16, 1);
+  if (!d) return mij_last_error();
+  int rc = mij_decoder_decode(d, &jpg, &len, 1);
+  if (!rc) rc = mij_decoder_reconstruct_scaled(d, order, denom);
   if (!rc) rc = mij_decoder_pixels(d, 0, out, cap, 0);
   decoder_free(d);  // (leaves the failure's message in place)
   return rc;

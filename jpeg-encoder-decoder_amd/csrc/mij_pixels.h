@@ -325,4 +325,145 @@ MIJ_HD void colour_tile_any(const uint8_t *Y, const uint8_t *Cb, const uint8_t *
   }
 }
 
+// ---------------------------------------------------------------------------
+// Decoding at 1/2, 1/4 and 1/8 scale: libjpeg's reduced IDCTs
+// (jidctred.c), which give a 4x4, 2x2 or 1x1 block from the low frequencies,
+// and the geometry that goes with them.  Products and sums modulo 2^32 as in
+// idct8.
+// ---------------------------------------------------------------------------
+template <int SH>
+MIJ_HD void idct4_1d(uint32_t i0, uint32_t i1, uint32_t i2, uint32_t i3, uint32_t i5, uint32_t i6, uint32_t i7,
+                     int32_t o[4]) {
+  const uint32_t t0 = i0 << 14, t2 = i2 * 15137u - i6 * 6270u;
+  const uint32_t t10 = t0 + t2, t12 = t0 - t2;
+  const uint32_t a = i5 * 11893u + i1 * 8697u - i7 * 1730u - i3 * 17799u;
+  const uint32_t b = i3 * 7373u + i1 * 20995u - i7 * 4176u - i5 * 4926u;
+  constexpr uint32_t R = 1u << (SH - 1);
+  o[0] = (int32_t)(t10 + b + R) >> SH;
+  o[1] = (int32_t)(t12 + a + R) >> SH;
+  o[2] = (int32_t)(t12 - a + R) >> SH;
+  o[3] = (int32_t)(t10 - b + R) >> SH;
+}
+
+// One block at 1/2 scale: c, dc, qz as idct_block; rows[r] = the 4 samples of
+// row r in one little-endian word.  Column 4 and row 4 of the block are never
+// used (jpeg_idct_4x4).
+MIJ_HD void idct4_block(const int16_t *c, uint32_t dc, const int32_t *qz, uint32_t rows[4]) {
+  constexpr uint8_t zz[64] = MIJ_ZIGZAG;
+  uint32_t d[64];
+  d[0] = dc * (uint32_t)qz[0];
+  MIJ_UNROLL
+  for (int z = 1; z < 64; z++) d[zz[z]] = (uint32_t)(int32_t)c[z] * (uint32_t)qz[z];
+  int32_t ws[4][8];
+  MIJ_UNROLL
+  for (int col = 0; col < 8; col++) {  // down each column but 4, descale 12
+    int32_t o[4] = {0, 0, 0, 0};
+    if (col != 4) idct4_1d<12>(d[col], d[8 + col], d[16 + col], d[24 + col], d[40 + col], d[48 + col], d[56 + col], o);
+  MIJ_UNROLL
+    for (int k = 0; k < 4; k++) ws[k][col] = o[k];
+  }
+  MIJ_UNROLL
+  for (int r = 0; r < 4; r++) {  // along each row, descale 19, level shift, clamp
+    int32_t o[4];
+    idct4_1d<19>(ws[r][0], ws[r][1], ws[r][2], ws[r][3], ws[r][5], ws[r][6], ws[r][7], o);
+    rows[r] = clamp255(o[0] + 128) | clamp255(o[1] + 128) << 8 | clamp255(o[2] + 128) << 16 |
+              clamp255(o[3] + 128) << 24;
+  }
+}
+
+template <int SH>
+MIJ_HD void idct2_1d(uint32_t i0, uint32_t i1, uint32_t i3, uint32_t i5, uint32_t i7, int32_t o[2]) {
+  const uint32_t t10 = i0 << 15;
+  const uint32_t t0 = i5 * 6967u + i1 * 29692u - i7 * 5906u - i3 * 10426u;
+  constexpr uint32_t R = 1u << (SH - 1);
+  o[0] = (int32_t)(t10 + t0 + R) >> SH;
+  o[1] = (int32_t)(t10 - t0 + R) >> SH;
+}
+
+// One block at 1/4 scale: rows[r] = the 2 samples of row r in the low 16 bits.
+// Only rows and columns 0, 1, 3, 5, 7 of the block are used (jpeg_idct_2x2).
+MIJ_HD void idct2_block(const int16_t *c, uint32_t dc, const int32_t *qz, uint32_t rows[2]) {
+  constexpr uint8_t zz[64] = MIJ_ZIGZAG;
+  uint32_t d[64];
+  d[0] = dc * (uint32_t)qz[0];
+  MIJ_UNROLL
+  for (int z = 1; z < 64; z++) d[zz[z]] = (uint32_t)(int32_t)c[z] * (uint32_t)qz[z];
+  int32_t ws[2][8];
+  MIJ_UNROLL
+  for (int col = 0; col < 8; col++) {  // down columns 0, 1, 3, 5, 7, descale 13
+    int32_t o[2] = {0, 0};
+    if (col < 2 || (col & 1)) idct2_1d<13>(d[col], d[8 + col], d[24 + col], d[40 + col], d[56 + col], o);
+    ws[0][col] = o[0];
+    ws[1][col] = o[1];
+  }
+  MIJ_UNROLL
+  for (int r = 0; r < 2; r++) {  // along each row, descale 20, level shift, clamp
+    int32_t o[2];
+    idct2_1d<20>(ws[r][0], ws[r][1], ws[r][3], ws[r][5], ws[r][7], o);
+    rows[r] = clamp255(o[0] + 128) | clamp255(o[1] + 128) << 8;
+  }
+}
+
+// One block at 1/8 scale: the DC alone (jpeg_idct_1x1)
+MIJ_HD uint32_t idct1_block(uint32_t dc, int32_t q0) {
+  return clamp255(((int32_t)(dc * (uint32_t)q0 + 4u) >> 3) + 128);
+}
+
+// The geometry of a frame decoded at 1/denom (denom 1, 2, 4 or 8), libjpeg's
+// rules (jdmaster.c): s = 8 / denom output samples per 8 input samples; a
+// component's IDCT size S starts at s and doubles while it stays <= 8 and
+// the component would otherwise be upsampled by a multiple of 2 both across
+// and down, so 4:2:0 chroma is scaled up inside its IDCT and needs no
+// upsampler, and 4:2:2 keeps its horizontal one.  Shared by the host
+// planner, the kernels' job tables and tests/scaled_check.cpp.
+struct ScaledComp {
+  int S;       // the IDCT's output size: S x S samples per block
+  int cw, ch;  // the component's real size in samples
+  int pitch;   // bytes between rows of its padded plane: S * blocks across, rounded up to 8
+  int rows;    // rows of the padded plane: S * blocks down
+};
+
+struct ScaledGeom {
+  int ow, oh;  // the output's size
+  int mode;    // PIX_* for colour_tile_any on the scaled planes
+  ScaledComp c[3];
+};
+
+// hs / vs / bw / bh: per component sampling factors and padded plane in
+// blocks (a single component: 1 x 1)
+MIJ_HD void scaled_geometry(int w, int h, int ncomp, const int *hs, const int *vs, const int *bw, const int *bh,
+                            int denom, ScaledGeom &G) {
+  const int s = 8 / denom;
+  int hmax = 1, vmax = 1;
+  for (int c = 0; c < ncomp; c++) {
+    hmax = hs[c] > hmax ? hs[c] : hmax;
+    vmax = vs[c] > vmax ? vs[c] : vmax;
+  }
+  G.ow = (int)(((long long)w * s + 7) / 8);
+  G.oh = (int)(((long long)h * s + 7) / 8);
+  int fx = 1, fy = 1;
+  for (int c = 0; c < 3; c++) {
+    ScaledComp &C = G.c[c];
+    if (c >= ncomp) {
+      C = G.c[0];
+      continue;
+    }
+    int S = s;
+    while (S < 8 && (hmax * s) % (hs[c] * S * 2) == 0 && (vmax * s) % (vs[c] * S * 2) == 0) S *= 2;
+    C.S = S;
+    C.cw = (int)(((long long)w * hs[c] * S + hmax * 8LL - 1) / (hmax * 8LL));
+    C.ch = (int)(((long long)h * vs[c] * S + vmax * 8LL - 1) / (vmax * 8LL));
+    C.pitch = (S * bw[c] + 7) / 8 * 8;
+    C.rows = S * bh[c];
+    if (c) {
+      fx = hmax * s / (hs[c] * S);
+      fy = vmax * s / (vs[c] * S);
+    }
+  }
+  if (ncomp == 1) G.mode = PIX_GREY;
+  else if (fx == 1 && fy == 1) G.mode = PIX_444;
+  else if (fy == 1) G.mode = (G.c[1].cw > 2 && s > 1) ? PIX_H2V1 : PIX_H2V1_REP;  // libjpeg: no fancy upsampling at IDCT size 1
+  else G.mode = (G.c[1].cw > 2 && s > 1) ? PIX_H2V2 : PIX_H2V2_REP;
+}
+
 }  // namespace mij

@@ -8,11 +8,15 @@
  * colour conversion all run on the GPU.  Anything else is refused with the
  * reason.
  *
- *   decode_jpg <in.jpg> <out.ppm>
+ * With -scale 1/2, 1/4 or 1/8 the image comes out at that scale through
+ * mij_decode_scaled, as djpeg -scale gives it (libjpeg's reduced IDCTs).
+ *
+ *   decode_jpg [-scale 1/N] <in.jpg> <out.ppm>
  */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "mijpeg.h"
 
@@ -34,8 +38,19 @@ static uint8_t *read_file(const char *path, size_t *len) {
 }
 
 int main(int argc, char **argv) {
+    int denom = 1;
+    const char *prog = argv[0];
+    if (argc == 5 && !strcmp(argv[1], "-scale")) {
+        char tail = 0;
+        if (sscanf(argv[2], "1/%d%c", &denom, &tail) != 1 || (denom != 1 && denom != 2 && denom != 4 && denom != 8)) {
+            fprintf(stderr, "%s: -scale %s: 1/1, 1/2, 1/4 or 1/8\n", prog, argv[2]);
+            return 2;
+        }
+        argv += 2;
+        argc -= 2;
+    }
     if (argc != 3) {
-        fprintf(stderr, "usage: %s <in.jpg> <out.ppm>\n", argv[0]);
+        fprintf(stderr, "usage: %s [-scale 1/N] <in.jpg> <out.ppm>\n", prog);
         return 2;
     }
     size_t len = 0;
@@ -45,7 +60,7 @@ int main(int argc, char **argv) {
      * that reports the size and MIJ_ENOSPC before any device work */
     int w = 0, h = 0;
     uint8_t probe;
-    int rc = mij_decode(jpg, len, MIJ_PIX_RGB, &probe, 0, &w, &h);
+    int rc = mij_decode_scaled(jpg, len, MIJ_PIX_RGB, denom, &probe, 0, &w, &h);
     if (rc != MIJ_ENOSPC) {
         fprintf(stderr, "%s: %s: %s\n", argv[1], mij_strerror(rc), mij_last_message());
         return 1;
@@ -53,7 +68,7 @@ int main(int argc, char **argv) {
     size_t cap = (size_t)3 * w * h;
     uint8_t *px = malloc(cap);
     if (!px) { fprintf(stderr, "out of memory\n"); return 1; }
-    rc = mij_decode(jpg, len, MIJ_PIX_RGB, px, cap, &w, &h);
+    rc = mij_decode_scaled(jpg, len, MIJ_PIX_RGB, denom, px, cap, &w, &h);
     if (rc != MIJ_OK) {
         fprintf(stderr, "%s: %s: %s\n", argv[1], mij_strerror(rc), mij_last_message());
         return 1;

@@ -52,6 +52,7 @@ EXPORTS = [
     "mij_decoder_transcode", "mij_decoder_transcoded", "mij_decoder_device_transcoded", "mij_decoder_transcode_ms",
     "mij_transcode",
     "mij_decoder_transform", "mij_transform", "mij_exif_orientation", "mij_orientation_op",
+    "mij_decoder_reconstruct_scaled", "mij_decoder_scaled_layout", "mij_decode_scaled",
 ]
 
 
@@ -251,6 +252,9 @@ def load() -> C.CDLL:
         lib.mij_transform.argtypes = [p, sz, i, i, C.POINTER(Area), i, p, sz, C.POINTER(sz)]
         lib.mij_exif_orientation.argtypes = [p, sz]
         lib.mij_orientation_op.argtypes = [i]
+        lib.mij_decoder_reconstruct_scaled.argtypes = [p, i, i]
+        lib.mij_decoder_scaled_layout.argtypes = [p, i, i, p, i]
+        lib.mij_decode_scaled.argtypes = [p, sz, i, i, p, sz, C.POINTER(i), C.POINTER(i)]
     except AttributeError:
         if not os.environ.get("MIJ_LIB"):  # older builds only in A/B timing runs
             raise
@@ -947,18 +951,28 @@ def _order(order: str) -> int:
     return PIXEL_ORDERS[order]
 
 
-def decode(jpg: bytes, order: str = "bgr") -> np.ndarray:
-    """mij_decode: one baseline JFIF stream -> (h, w, 3) uint8 pixels, host to host."""
+def decode(jpg: bytes, order: str = "bgr", scale: int = 1) -> np.ndarray:
+    """mij_decode: one baseline JFIF stream -> (h, w, 3) uint8 pixels, host to
+    host; scale = 2, 4, 8: mij_decode_scaled, the image at 1/scale as
+    libjpeg's reduced IDCTs give it."""
     lib = load()
     buf = np.frombuffer(jpg, np.uint8)
     w, h = C.c_int(0), C.c_int(0)
     probe = np.zeros(1, np.uint8)
-    rc = lib.mij_decode(_ptr(buf), buf.size, _order(order), _ptr(probe), 0, C.byref(w), C.byref(h))
+    if scale == 1:
+        def call(dst, cap):
+            return lib.mij_decode(_ptr(buf), buf.size, _order(order), _ptr(dst), cap, C.byref(w), C.byref(h))
+        what = "mij_decode"
+    else:
+        def call(dst, cap):
+            return lib.mij_decode_scaled(_ptr(buf), buf.size, _order(order), int(scale), _ptr(dst), cap, C.byref(w),
+                                         C.byref(h))
+        what = "mij_decode_scaled"
+    rc = call(probe, 0)
     if rc != 4:  # MIJ_ENOSPC once the size is known, before any device work
-        _check(rc, "mij_decode")
+        _check(rc, what)
     out = np.zeros((h.value, w.value, 3), np.uint8)
-    _check(lib.mij_decode(_ptr(buf), buf.size, _order(order), _ptr(out), out.nbytes, C.byref(w), C.byref(h)),
-           "mij_decode")
+    _check(call(out, out.nbytes), what)
     return out
 
 
@@ -1037,6 +1051,7 @@ class Decoder:
 
     def __init__(self, max_w: int, max_h: int, max_frames: int, device: int = 0):
         self.lib = load()
+        self.scale_ = 1  # of the last reconstruct
         self.h_ = self.lib.mij_decoder_create(device, max_w, max_h, max_frames)
         if not self.h_:
             raise MijError("mij_decoder_create failed: "
@@ -1095,22 +1110,48 @@ class Decoder:
         _check(self.lib.mij_decoder_component(self.h_, frame, comp, _ptr(out), out.size), "decoder_component")
         return out
 
+    def scaled_layout(self, frame: int, scale: int) -> dict:
+        """mij_decoder_scaled_layout: the frame's geometry at 1/scale; comps: (S, cw, ch, pitch, rows)"""
+        out = np.zeros(18, np.int32)
+        _check(self.lib.mij_decoder_scaled_layout(self.h_, frame, int(scale), _ptr(out), out.size),
+               "decoder_scaled_layout")
+        v = [int(x) for x in out]
+        lay = {"w": v[0], "h": v[1], "ncomp": v[2]}
+        lay["comps"] = [tuple(v[3 + 5 * c:8 + 5 * c]) for c in range(v[2])]
+        lay["raw"] = v[:3 + 5 * v[2]]
+        return lay
+
     def plane(self, frame: int, comp: int) -> np.ndarray:
-        """(8 * blocks down, 8 * blocks across) uint8: the padded sample plane after the IDCT"""
+        """(8 * blocks down, 8 * blocks across) uint8: the padded sample plane
+        after the IDCT; after a scaled reconstruct (rows, pitch) of scaled_layout"""
+        if self.scale_ > 1:
+            _, _, _, pitch, rows = self.scaled_layout(frame, self.scale_)["comps"][comp]
+            out = np.zeros((rows, pitch), np.uint8)
+            _check(self.lib.mij_decoder_plane(self.h_, frame, comp, _ptr(out), out.nbytes), "decoder_plane")
+            return out
         _, _, _, bw, bh = self.layout(frame)["comps"][comp]
         out = np.zeros((8 * bh, 8 * bw), np.uint8)
         _check(self.lib.mij_decoder_plane(self.h_, frame, comp, _ptr(out), out.nbytes), "decoder_plane")
         return out
 
-    def reconstruct(self, order: str = "bgr") -> None:
-        """every frame of the last decode -> planes and pixels (asynchronous)"""
-        _check(self.lib.mij_decoder_reconstruct(self.h_, _order(order)), "decoder_reconstruct")
+    def reconstruct(self, order: str = "bgr", scale: int = 1) -> None:
+        """every frame of the last decode -> planes and pixels (asynchronous);
+        scale = 2, 4, 8: at 1/scale (mij_decoder_reconstruct_scaled), and
+        pixels / plane / device_pixels then serve the scaled result"""
+        if scale == 1:
+            _check(self.lib.mij_decoder_reconstruct(self.h_, _order(order)), "decoder_reconstruct")
+        else:
+            _check(self.lib.mij_decoder_reconstruct_scaled(self.h_, _order(order), int(scale)),
+                   "decoder_reconstruct_scaled")
+        self.scale_ = int(scale)
 
     def pixels(self, frame: int, pitch: int = 0, out: np.ndarray | None = None) -> np.ndarray:
         """(h, w, 3) uint8 pixels of `frame`; with `pitch` (bytes, >= 3*w) the
         rows land pitch bytes apart in `out` (a flat uint8 array, or a new
         one), whose other bytes are left as they are"""
         w, h, _ = self.info(frame)
+        if self.scale_ > 1:
+            w, h = self.scaled_layout(frame, self.scale_)["raw"][:2]
         if not pitch:
             out = np.zeros((h, w, 3), np.uint8)
         elif out is None:
