@@ -306,6 +306,47 @@ int mij_batch_encode_interleaved(mij_batch *b, int nframes, int restart_rows);
 int mij_encode_any(const uint8_t *px, int stride_px, int w, int h, int order, int quality,
                    int restart_rows, uint8_t *out, size_t cap, size_t *out_len);
 
+/* ---- a chosen chroma sampling -------------------------------
+ * The interleaved format above at 4:2:0, 4:2:2, 4:4:4 or greyscale.  Hmax x
+ * Vmax is 2x2, 2x1, 1x1, 1x1 and an MCU 8 Hmax x 8 Vmax pixels; the frame is
+ * edge-extended to whole MCUs (the padded slots hold that extension for every
+ * sampling).  Every pixel gets Y, Cb, Cr by the reference's expressions,
+ * truncated; 4:4:4 chroma is those bytes, 4:2:2 chroma (a + b) / 2 over a
+ * horizontal pair of them, greyscale has one component (one DQT, two DHT).
+ * DCT, truncating quantisation, clip and zigzag are the reference's on every
+ * 8x8 block of every plane, luma table for component 0, chroma table for the
+ * others.  restart_rows counts MCU rows of the sampling's grid (8 pixel rows
+ * for all but 4:2:0): Ri = r * ceil(w / (8 Hmax)).  MIJ_SAMP_420 is, byte for
+ * byte, mij_batch_encode_interleaved / mij_encode_any. */
+enum { MIJ_SAMP_420 = 0, MIJ_SAMP_422 = 1, MIJ_SAMP_444 = 2, MIJ_SAMP_GRAY = 3 };
+/* Worst-case size of such a stream: the per-block worst case of
+ * mij_max_jpg_bytes times the sampling's blocks, headers, the DRI segment, 2
+ * bytes per restart marker; mij_max_jpg_bytes_any for MIJ_SAMP_420.  0 for
+ * sizes outside 1..65535, an unknown sampling, restart_rows < 0 or
+ * Ri > 65535.  Host only. */
+size_t mij_max_jpg_bytes_sampled(int w, int h, int sampling, int restart_rows);
+/* mij_batch_encode_interleaved at a sampling: slots 0..nframes-1 must hold
+ * padded input (mij_batch_pad_input / _upload_any) with mij_batch_set_rgb
+ * unchanged since; results through mij_batch_output / _lengths.  Waits for
+ * the device once mid-call (the frames' bit counts size the scan words).  A
+ * frame that fails (tables, capacity) has length 0 and its error code.  The
+ * first call with a sampling other than MIJ_SAMP_420 allocates this path's
+ * buffers, which grow with later calls, and grows the per-frame output
+ * capacity to mij_max_jpg_bytes_sampled of the canvas. */
+int mij_batch_encode_sampled(mij_batch *b, int nframes, int sampling, int restart_rows);
+/* The planes the last mij_batch_encode_sampled coded, as mij_decoder_layout
+ * and mij_decoder_component show a decoded stream's: layout = {w, h, ncomp,
+ * hmax, vmax, mcus_x, mcus_y, Ri, 1} then {h, v, tq, blocks across, blocks
+ * down} per component (MIJ_ENOSPC under 9 + 5 * ncomp ints); a component =
+ * its padded plane, raster blocks of 64 zigzag coefficients, DC absolute. */
+int mij_batch_sampled_layout(mij_batch *b, int frame, int *out, int n);
+int mij_batch_sampled_component(mij_batch *b, int frame, int comp, int16_t *dst, size_t cap);
+/* mij_encode_any at a sampling.  Every MIJ_EINVAL, and MIJ_ENOSPC with
+ * mij_max_jpg_bytes_sampled(w, h, sampling, restart_rows) in *out_len when
+ * cap is under it, come before any device work. */
+int mij_encode_sampled(const uint8_t *px, int stride_px, int w, int h, int order, int quality,
+                       int sampling, int restart_rows, uint8_t *out, size_t cap, size_t *out_len);
+
 /* ---- PPM ingest -----------------------------------
  * Header rules of the reference's reader, utils/original.c:294-365, kept
  * exactly: "P6" then a newline straight after it; then lines up to the first

@@ -14,6 +14,8 @@
 #include "mij_host.h"
 #include "mij_internal.h"
 #include "mij_interleave.h"
+#include "mij_sampled.h"
+#include "mij_transcode.h"
 #include "mijpeg.h"
 #include "mij_testing.h"
 
@@ -397,6 +399,24 @@ struct mij_batch {
   uint32_t *d_il_mcu_off = nullptr, *d_il_row_bits = nullptr, *d_il_ffc = nullptr;
   uint64_t *d_il_row_pre = nullptr, *d_il_ival = nullptr, *d_il_row_off = nullptr;
   int *d_il_hdr = nullptr;
+  // a chosen sampling (mij_batch_encode_sampled): nothing here
+  // exists before the first encode at a sampling other than 4:2:0; the
+  // device arrays (SB_*) grow to what a call needs
+  struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+  };
+  enum { SB_PLANE, SB_ABS, SB_FR, SB_TFR, SB_TOUT, SB_BLK_BITS, SB_MCU_OFF, SB_ROW_BITS, SB_ROW_PRE, SB_IVAL,
+         SB_ROW_OFF, SB_BITS, SB_HDR, SB_RAW, SB_FFC, SB_COUNT };
+  DevBuf sb[SB_COUNT];
+  int samp_last = -1;  // sampling of the last mij_batch_encode_sampled (-1: none)
+  int samp_n = 0, samp_rr = 0;   // its frames and restart_rows
+  std::vector<int2> samp_wh;     // its frames' true sizes
+  std::vector<SampFrame> h_sfr;
+  std::vector<TcFrame> h_stf;
+  std::vector<TcOut> h_sto;
+  int samp_test_frame = -1;      // mij_test_sampled_out_cap: the next sampled encode's
+  long long samp_test_cap = 0;   // frame with this output capacity at most
 };
 
 template <class T>
@@ -425,6 +445,8 @@ static void batch_free(mij_batch *b) {
                   b->d_il_ffc, b->d_il_row_pre, b->d_il_ival, b->d_il_row_off, b->d_il_hdr};
   for (void *p : ptrs)
     if (p) hipFree(p);
+  for (mij_batch::DevBuf &d : b->sb)
+    if (d.p) hipFree(d.p);
   for (auto &row : b->evh)
     for (auto &e : row)
       if (e) hipEventDestroy(e);
@@ -2471,6 +2493,364 @@ extern "C" int mij_encode_any(const uint8_t *px, int stride_px, int w, int h, in
   b->rgb = order == MIJ_PIX_RGB;
   if (mij_batch_upload_any(b, px, stride_px, w, h, 0)) return g_err;
   if (mij_batch_encode_interleaved(b, 1, restart_rows)) return g_err;
+  size_t n = 0;
+  if (mij_batch_output(b, 0, out, cap, &n)) return g_err;
+  if (out_len) *out_len = n;
+  return MIJ_OK;
+}
+
+// ---------------------------------------------------------------------------
+// a chosen chroma sampling: the padded slots through
+// k_samp_dct (mij_sampled.hip) into planes of the sampling's block grid, then
+// the transcoder's entropy coder (mij_transcode.hip) over those planes.
+// 4:2:0 is the interleaved format above, unchanged.
+// ---------------------------------------------------------------------------
+static bool samp_known(int s) { return s >= MIJ_SAMP_420 && s <= MIJ_SAMP_GRAY; }
+
+// restart markers of a w x h frame at a sampling; -1: Ri > 65535
+static long long samp_markers(int w, int h, int sampling, int restart_rows) {
+  if (restart_rows <= 0) return 0;
+  const SampGrid g = samp_grid(w, h, sampling);
+  if ((long long)restart_rows * g.mcus_x > 65535) return -1;
+  return (g.mcus_y + restart_rows - 1) / restart_rows - 1;
+}
+
+// make_geom's out_cap for a count of blocks
+static long long samp_block_bytes(long long nblk) { return round_up(nblk * 434 + 4096, 256); }
+
+extern "C" size_t mij_max_jpg_bytes_sampled(int w, int h, int sampling, int restart_rows) {
+  if (w < 1 || h < 1 || w > 65535 || h > 65535 || restart_rows < 0 || !samp_known(sampling)) return 0;
+  if (sampling == MIJ_SAMP_420) return mij_max_jpg_bytes_any(w, h, restart_rows);
+  const long long mk = samp_markers(w, h, sampling, restart_rows);
+  if (mk < 0) return 0;
+  return (size_t)(samp_block_bytes(samp_grid(w, h, sampling).nblk) + 2 * mk + (restart_rows ? 6 : 0));
+}
+
+// test-only (csrc/mij_testing.h): the next sampled encode gives `frame` an
+// output capacity of at most `cap` bytes
+extern "C" int mij_test_sampled_out_cap(mij_batch *b, int frame, long long cap) {
+  if (!b || frame < 0 || frame >= b->cap || cap < 0) return fail(MIJ_EINVAL, "test_sampled_out_cap: bad args"), -2;
+  b->samp_test_frame = frame;
+  b->samp_test_cap = cap;
+  return MIJ_OK;
+}
+
+static int samp_grow(mij_batch *b, int which, size_t bytes) {
+  mij_batch::DevBuf &d = b->sb[which];
+  if (bytes <= d.bytes) return MIJ_OK;
+  // the new buffer first: a failed allocation leaves the batch as it was
+  void *p = nullptr;
+  HIP_TRY(hipMalloc(&p, bytes + 256));
+  hipStreamSynchronize(b->stream);
+  if (d.p) hipFree(d.p);
+  d.p = p;
+  d.bytes = bytes;
+  return MIJ_OK;
+}
+
+template <class T>
+static T *samp_buf(mij_batch *b, int which) {
+  return (T *)b->sb[which].p;
+}
+
+// Waits for the device twice: before the descriptors are rebuilt (the last
+// call's uploads read them) and for the frames' bits, which size the scan
+// words; the write and the lengths stay asynchronous.
+extern "C" int mij_batch_encode_sampled(mij_batch *b, int nframes, int sampling, int restart_rows) {
+  if (pipe_check(b, "encode_sampled")) return g_err;
+  if (!samp_known(sampling)) return fail(MIJ_EINVAL, "encode_sampled: sampling %d (MIJ_SAMP_420 .. MIJ_SAMP_GRAY)", sampling);
+  if (nframes < 1 || nframes > b->cap) return fail(MIJ_EINVAL, "encode_sampled: bad frame count %d", nframes);
+  if (restart_rows < 0) return fail(MIJ_EINVAL, "encode_sampled: restart_rows %d", restart_rows);
+  long long markers = 0;
+  for (int i = 0; i < nframes; i++) {
+    if (i >= (int)b->il_slot.size() || b->il_slot[i].x == 0)
+      return fail(MIJ_EINVAL, "encode_sampled: slot %d holds no padded input (pad_input / upload_any first)", i);
+    const int4 s = b->il_slot[i];
+    if (s.z != (b->rgb ? 1 : 0)) return fail(MIJ_EINVAL, "encode_sampled: set_rgb changed after slot %d was padded", i);
+    const long long mk = samp_markers(s.x, s.y, sampling, restart_rows);
+    if (mk < 0)
+      return fail(MIJ_EINVAL, "encode_sampled: restart interval of %d rows x %d MCUs is over 65535 MCUs (slot %d)",
+                  restart_rows, samp_grid(s.x, s.y, sampling).mcus_x, i);
+    markers = std::max(markers, mk);
+  }
+  b->samp_last = -1;
+  if (sampling == MIJ_SAMP_420) {
+    if (mij_batch_encode_interleaved(b, nframes, restart_rows)) return g_err;
+  } else {
+    HIP_TRY(hipSetDevice(b->dev));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    const int n = nframes;
+    // sizes of the per-call arrays
+    long long nblk = 0, nmcu = 0, nrows = 0;
+    int max_nblk = 0, max_rows = 0, max_tiles = 0;
+    for (int f = 0; f < n; f++) {
+      const SampGrid S = samp_grid(b->il_slot[f].x, b->il_slot[f].y, sampling);
+      nblk += S.nblk;
+      nmcu += (long long)S.mcus_x * S.mcus_y;
+      nrows += S.mcus_y;
+      max_nblk = (int)std::max<long long>(max_nblk, S.nblk);
+      max_rows = std::max(max_rows, S.mcus_y);
+    }
+    if (nblk > 0x7fff0000LL) return fail(MIJ_EINVAL, "encode_sampled: too many blocks");
+#define SB_GROW(which, T, cnt) \
+  if (samp_grow(b, mij_batch::which, sizeof(T) * (size_t)(cnt))) return g_err
+    SB_GROW(SB_PLANE, int16_t, nblk * 64);
+    SB_GROW(SB_ABS, int16_t, nblk);
+    SB_GROW(SB_FR, SampFrame, n);
+    SB_GROW(SB_TFR, TcFrame, n);
+    SB_GROW(SB_TOUT, TcOut, n);
+    SB_GROW(SB_BLK_BITS, uint16_t, nblk);
+    SB_GROW(SB_MCU_OFF, uint32_t, nmcu);
+    SB_GROW(SB_ROW_BITS, uint32_t, nrows);
+    SB_GROW(SB_ROW_PRE, uint64_t, nrows + n);
+    SB_GROW(SB_IVAL, uint64_t, nrows + n);
+    SB_GROW(SB_ROW_OFF, uint64_t, nrows + n);
+    SB_GROW(SB_BITS, uint64_t, n);
+    SB_GROW(SB_HDR, int, n);
+    // the per-frame output capacity covers mij_max_jpg_bytes_sampled of the canvas
+    const long long need =
+        round_up(samp_block_bytes(samp_grid(b->g.w, b->g.h, sampling).nblk) +
+                     2 * std::max(markers, samp_markers(b->g.w, b->g.h, sampling, restart_rows)) + (restart_rows ? 6 : 0),
+                 256);
+    if (need > b->g.out_cap) {
+      uint8_t *grown = nullptr;
+      HIP_TRY(dalloc(&grown, (long long)b->cap * need));
+      HIP_TRY(hipStreamSynchronize(b->stream));
+      hipFree(b->d_out);
+      b->d_out = grown;
+      b->g.out_cap = need;
+    }
+    // descriptors: the front end's and the coder's views of the same planes
+    int q[2][64];
+    quality_tables(b->quality, q[0], q[1]);
+    b->h_sfr.assign(n, SampFrame());
+    b->h_stf.assign(n, TcFrame());
+    long long pb = 0, b0 = 0, m0 = 0, r0 = 0;
+    for (int f = 0; f < n; f++) {
+      const int w = b->il_slot[f].x, h = b->il_slot[f].y;
+      const SampGrid S = samp_grid(w, h, sampling);
+      SampFrame &Q = b->h_sfr[f];
+      TcFrame &F = b->h_stf[f];
+      memset(&Q, 0, sizeof Q);
+      memset(&F, 0, sizeof F);
+      Q.w16 = il_round16(w);
+      Q.h16 = il_round16(h);
+      Q.tiles_x = (Q.w16 + SAMP_TW - 1) / SAMP_TW;
+      Q.ntiles = Q.tiles_x * (Q.h16 / SAMP_TH);
+      max_tiles = std::max(max_tiles, Q.ntiles);
+      F.ncomp = S.ncomp;
+      for (int c = 0; c < S.ncomp; c++) {
+        Q.plane[c] = samp_buf<int16_t>(b, mij_batch::SB_PLANE) + 64 * pb;
+        Q.abs[c] = samp_buf<int16_t>(b, mij_batch::SB_ABS) + pb;
+        Q.bw[c] = S.bw[c];
+        Q.bh[c] = S.bh[c];
+        pb += (long long)S.bw[c] * S.bh[c];
+        TcComp &C = F.c[c];
+        C.plane = Q.plane[c];
+        C.abs = Q.abs[c];
+        C.hs = S.hs[c];
+        C.vs = S.vs[c];
+        C.bw = S.bw[c];
+        F.bpm += S.hs[c] * S.vs[c];
+        F.sof[c][0] = (uint8_t)(c + 1);
+        F.sof[c][1] = (uint8_t)(S.ncomp > 1 ? (S.hs[c] << 4) | S.vs[c] : 0x11);
+        F.sof[c][2] = (uint8_t)(c ? 1 : 0);
+      }
+      F.mcus_x = S.mcus_x;
+      F.mcus_y = S.mcus_y;
+      F.R = restart_rows > 0 && restart_rows < S.mcus_y ? restart_rows : S.mcus_y;
+      F.nint = (S.mcus_y + F.R - 1) / F.R;
+      F.ri = restart_rows * S.mcus_x;
+      F.nblk = S.mcus_x * S.mcus_y * F.bpm;
+      F.blk0 = b0;
+      F.mcu0 = (int)m0;
+      F.row0 = (int)r0;
+      F.rowp0 = (int)r0 + f;
+      F.w = w;
+      F.h = h;
+      F.ndqt = S.ncomp > 1 ? 2 : 1;
+      for (int t = 0; t < F.ndqt; t++) {
+        F.dqt_id[t] = (uint8_t)t;
+        for (int z = 0; z < 64; z++) F.dqt[t][z] = (uint8_t)q[t][k_zz[z]];
+      }
+      b0 += F.nblk;
+      m0 += (long long)S.mcus_x * S.mcus_y;
+      r0 += S.mcus_y;
+    }
+    next_slot(b);
+    SampFrame *d_fr = samp_buf<SampFrame>(b, mij_batch::SB_FR);
+    TcFrame *d_tf = samp_buf<TcFrame>(b, mij_batch::SB_TFR);
+    TcOut *d_to = samp_buf<TcOut>(b, mij_batch::SB_TOUT);
+    HIP_TRY(hipMemcpyAsync(d_fr, b->h_sfr.data(), n * sizeof(SampFrame), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(d_tf, b->h_stf.data(), n * sizeof(TcFrame), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemsetAsync(b->d_hist, 0, sizeof(uint32_t) * n * 4 * 257, b->stream));
+    HIP_TRY(hipMemsetAsync(b->d_err, 0, sizeof(int) * n, b->stream));
+    b->hist_zero_n = b->band_hist_zero = 0;
+    b->k1_err_zero = 0;
+    if (b->timing) HIP_TRY(hipEventRecord(b->ev[0], b->stream));
+    SampArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.in = b->d_in;
+    sa.in_fs = b->in_fs;
+    sa.pitch = b->pitch;
+    sa.sampling = sampling;
+    sa.fr = d_fr;
+    sa.tab = b->d_tab;
+    HIP_TRY(launch_samp_dct(sa, n, max_tiles, b->stream));
+    if (b->timing)
+      for (int e = 1; e <= 3; e++) HIP_TRY(hipEventRecord(b->ev[e], b->stream));
+    TcArgs a;
+    memset(&a, 0, sizeof a);
+    a.fr = d_tf;
+    a.o = d_to;
+    a.nframes = n;
+    a.max_nblk = max_nblk;
+    a.max_rows = max_rows;
+    a.hist = b->d_hist;
+    a.ehuf = b->d_ehuf;
+    a.hc = b->d_hc;
+    a.blk_bits = samp_buf<uint16_t>(b, mij_batch::SB_BLK_BITS);
+    a.mcu_off = samp_buf<uint32_t>(b, mij_batch::SB_MCU_OFF);
+    a.row_bits = samp_buf<uint32_t>(b, mij_batch::SB_ROW_BITS);
+    a.row_pre = samp_buf<unsigned long long>(b, mij_batch::SB_ROW_PRE);
+    a.ival_off = samp_buf<unsigned long long>(b, mij_batch::SB_IVAL);
+    a.row_off = samp_buf<unsigned long long>(b, mij_batch::SB_ROW_OFF);
+    a.bits = samp_buf<unsigned long long>(b, mij_batch::SB_BITS);
+    a.hdr = samp_buf<int>(b, mij_batch::SB_HDR);
+    a.out_len = b->d_out_len;
+    a.err = b->d_err;
+    HIP_TRY(launch_tc_hist(a, b->stream));
+    if (b->timing) HIP_TRY(hipEventRecord(b->ev[4], b->stream));
+    EntArgs e;  // k_tables_1w: one wave per table, all four of every frame
+    memset(&e, 0, sizeof e);
+    e.nframes = n;
+    e.hist = b->d_hist;
+    e.ehuf = b->d_ehuf;
+    e.hc = b->d_hc;
+    e.err = b->d_err;
+    HIP_TRY(launch_tables(e, b->stream));
+    if (b->timing) HIP_TRY(hipEventRecord(b->ev[5], b->stream));
+    HIP_TRY(launch_tc_sizes(a, b->stream));
+    // the frames' bits size the scan words and the chunks
+    std::vector<unsigned long long> bits(n);
+    HIP_TRY(hipMemcpyAsync(bits.data(), a.bits, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    b->h_sto.assign(n, TcOut());
+    long long raw = 0, chunks = 0, max_chunks = 0;
+    for (int f = 0; f < n; f++) {
+      TcOut &O = b->h_sto[f];
+      const long long nbytes = (long long)(bits[f] >> 3), nch = (nbytes + TC_CH - 1) / TC_CH;
+      O.raw0 = raw;
+      O.raw_words = round_up((long long)(bits[f] / 128 + 1) * 4, 64);
+      O.out0 = (long long)f * b->g.out_cap;
+      O.out_cap = b->g.out_cap;
+      if (f == b->samp_test_frame) O.out_cap = std::min(O.out_cap, b->samp_test_cap);
+      O.chunk0 = chunks;
+      raw += O.raw_words;
+      chunks += nch;
+      max_chunks = std::max(max_chunks, nch);
+    }
+    b->samp_test_frame = -1;
+    SB_GROW(SB_RAW, uint32_t, raw);
+    SB_GROW(SB_FFC, uint32_t, chunks + 1);
+#undef SB_GROW
+    HIP_TRY(hipMemcpyAsync(d_to, b->h_sto.data(), n * sizeof(TcOut), hipMemcpyHostToDevice, b->stream));
+    a.max_chunks = (int)std::min<long long>(max_chunks, 1 << 20);
+    a.raw = samp_buf<uint32_t>(b, mij_batch::SB_RAW);
+    a.ffc = samp_buf<uint32_t>(b, mij_batch::SB_FFC);
+    a.out = b->d_out;
+    HIP_TRY(launch_tc_write(a, b->stream));
+    if (b->timing) {
+      HIP_TRY(hipEventRecord(b->ev[6], b->stream));
+      HIP_TRY(hipEventRecord(b->ev[7], b->stream));
+    }
+    b->last_frames = nframes;
+  }
+  b->samp_wh.resize(nframes);
+  for (int i = 0; i < nframes; i++) b->samp_wh[i] = make_int2(b->il_slot[i].x, b->il_slot[i].y);
+  b->samp_last = sampling;
+  b->samp_n = nframes;
+  b->samp_rr = restart_rows;
+  return MIJ_OK;
+}
+
+static int samp_frame(mij_batch *b, int frame, const char *what) {
+  if (pipe_check(b, what)) return g_err;
+  if (b->samp_last < 0) return fail(MIJ_EINVAL, "%s: no mij_batch_encode_sampled yet", what);
+  if (frame < 0 || frame >= b->samp_n) return fail(MIJ_EINVAL, "%s: frame %d of %d", what, frame, b->samp_n);
+  return MIJ_OK;
+}
+
+extern "C" int mij_batch_sampled_layout(mij_batch *b, int frame, int *out, int n) {
+  if (samp_frame(b, frame, "sampled_layout")) return g_err;
+  if (!out) return fail(MIJ_EINVAL, "sampled_layout: out is NULL");
+  const int2 wh = b->samp_wh[frame];
+  const SampGrid S = samp_grid(wh.x, wh.y, b->samp_last);
+  const int need = 9 + 5 * S.ncomp;
+  if (n < need) return fail(MIJ_ENOSPC, "sampled_layout: need %d ints", need);
+  const int head[9] = {wh.x, wh.y, S.ncomp, S.hmax, S.vmax, S.mcus_x, S.mcus_y, b->samp_rr * S.mcus_x, 1};
+  memcpy(out, head, sizeof head);
+  for (int c = 0; c < S.ncomp; c++) {
+    const int e[5] = {S.hs[c], S.vs[c], c ? 1 : 0, S.bw[c], S.bh[c]};
+    memcpy(out + 9 + 5 * c, e, sizeof e);
+  }
+  return MIJ_OK;
+}
+
+extern "C" int mij_batch_sampled_component(mij_batch *b, int frame, int comp, int16_t *dst, size_t cap) {
+  if (samp_frame(b, frame, "sampled_component")) return g_err;
+  if (!dst) return fail(MIJ_EINVAL, "sampled_component: dst is NULL");
+  const int2 wh = b->samp_wh[frame];
+  const SampGrid S = samp_grid(wh.x, wh.y, b->samp_last);
+  if (comp < 0 || comp >= S.ncomp) return fail(MIJ_EINVAL, "sampled_component: component %d of %d", comp, S.ncomp);
+  const long long nb = (long long)S.bw[comp] * S.bh[comp];
+  if (cap < (size_t)(64 * nb)) return fail(MIJ_ENOSPC, "sampled_component: need %lld coefficients", 64 * nb);
+  const int16_t *src;
+  if (b->samp_last == MIJ_SAMP_420) {  // K1's planes of the padded frame: Y, Cb, Cr one after another
+    long long off = 0;
+    for (int c = 0; c < comp; c++) off += (long long)S.bw[c] * S.bh[c];
+    src = b->d_coef + (long long)frame * b->g.coef_fs + 64 * off;
+  } else {
+    src = b->h_sfr[frame].plane[comp];
+  }
+  HIP_TRY(hipSetDevice(b->dev));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  HIP_TRY(hipMemcpy(dst, src, (size_t)(128 * nb), hipMemcpyDeviceToHost));
+  return MIJ_OK;
+}
+
+extern "C" int mij_encode_sampled(const uint8_t *px, int stride_px, int w, int h, int order, int quality,
+                                  int sampling, int restart_rows, uint8_t *out, size_t cap, size_t *out_len) {
+  if (sampling == MIJ_SAMP_420)
+    return mij_encode_any(px, stride_px, w, h, order, quality, restart_rows, out, cap, out_len);
+  std::lock_guard<std::mutex> l(g_mu);
+  g_err = MIJ_OK;
+  if (!samp_known(sampling)) return fail(MIJ_EINVAL, "mij_encode_sampled: sampling %d (MIJ_SAMP_420 .. MIJ_SAMP_GRAY)", sampling);
+  if (w < 1 || h < 1 || w > 65535 || h > 65535)
+    return fail(MIJ_EINVAL, "mij_encode_sampled: frame %dx%d (1..65535 each)", w, h);
+  if (quality < 1 || quality > 100 || (order != MIJ_PIX_BGR && order != MIJ_PIX_RGB) || restart_rows < 0)
+    return fail(MIJ_EINVAL, "mij_encode_sampled: quality %d, order %d or restart_rows %d out of range", quality, order,
+                restart_rows);
+  if (samp_markers(w, h, sampling, restart_rows) < 0)
+    return fail(MIJ_EINVAL, "mij_encode_sampled: restart interval of %d rows x %d MCUs is over 65535 MCUs", restart_rows,
+                samp_grid(w, h, sampling).mcus_x);
+  const size_t bound = mij_max_jpg_bytes_sampled(w, h, sampling, restart_rows);
+  if (out_len) *out_len = bound;
+  if (cap < bound) return fail(MIJ_ENOSPC, "mij_encode_sampled: need %zu bytes for %dx%d", bound, w, h);
+  if (!px || !out || stride_px < w)
+    return fail(MIJ_EINVAL, "mij_encode_sampled: null buffer or stride %d under the width", stride_px);
+  const int W = il_round16(w), H = il_round16(h);
+  if (!g_actx || g_actx->g.w < W || g_actx->g.h < H || g_actx->quality != quality) {
+    const int cw = g_actx && g_actx->g.w > W ? g_actx->g.w : W;
+    const int ch = g_actx && g_actx->g.h > H ? g_actx->g.h : H;
+    batch_free(g_actx);
+    g_actx = mij_batch_create(drop_device(), cw, ch, 1, quality);
+    if (!g_actx) return g_err;
+  }
+  mij_batch *b = g_actx;
+  b->rgb = order == MIJ_PIX_RGB;
+  if (mij_batch_upload_any(b, px, stride_px, w, h, 0)) return g_err;
+  if (mij_batch_encode_sampled(b, 1, sampling, restart_rows)) return g_err;
   size_t n = 0;
   if (mij_batch_output(b, 0, out, cap, &n)) return g_err;
   if (out_len) *out_len = n;

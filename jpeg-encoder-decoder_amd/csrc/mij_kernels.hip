@@ -24,6 +24,7 @@
 
 #include "mij_internal.h"
 #include "mij_headers.h"
+#include "mij_colour_f64.h"
 
 namespace mij {
 
@@ -392,26 +393,8 @@ __device__ __forceinline__ void convert4(uint32_t w0, uint32_t w1, uint32_t w2, 
   o.cy = min(m01, m23) == 0u;
 }
 
-// The reference's colour expressions in FP64, operation for operation
-// (encoder.c:133-135: left to right, no contraction), truncated to uint8_t
-// (k_fix_blocks' recomputation of listed blocks).
-__device__ __forceinline__ int y_f64(uint32_t R, uint32_t G, uint32_t B) {
-  const double y = __dadd_rn(__dadd_rn(__dmul_rn(0.299, (double)R), __dmul_rn(0.587, (double)G)),
-                             __dmul_rn(0.114, (double)B));
-  return (int)(uint8_t)(int)y;
-}
-__device__ __forceinline__ int cb_f64(uint32_t R, uint32_t G, uint32_t B) {
-  const double v = __dadd_rn(__dadd_rn(__dadd_rn(128.0, -__dmul_rn(0.168736, (double)R)),
-                                       -__dmul_rn(0.331264, (double)G)),
-                             __dmul_rn(0.5, (double)B));
-  return (int)(uint8_t)(int)v;
-}
-__device__ __forceinline__ int cr_f64(uint32_t R, uint32_t G, uint32_t B) {
-  const double v = __dadd_rn(__dadd_rn(__dadd_rn(128.0, __dmul_rn(0.5, (double)R)),
-                                       -__dmul_rn(0.418688, (double)G)),
-                             -__dmul_rn(0.081312, (double)B));
-  return (int)(uint8_t)(int)v;
-}
+// (y_f64, cb_f64, cr_f64 -- the reference's colour expressions in FP64,
+// operation for operation -- are in mij_colour_f64.h.)
 
 // Rare path: the Y corrections of a run as a packed byte-wise subtrahend.
 // Only the pixel slots that hold an exact-integer Y in some lane pay for a

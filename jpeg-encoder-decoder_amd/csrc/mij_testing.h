@@ -44,6 +44,13 @@ enum {
   MIJ_PLAN_FIELDS
 };
 int mij_test_last_plan(mij_batch *b, int *out, int n);
+
+/* Capacity injection: the next mij_batch_encode_sampled at a sampling other
+ * than MIJ_SAMP_420 gives `frame` an output capacity of at most `cap` bytes
+ * (the public interface always sizes it for the worst case); that frame must
+ * fail alone with MIJ_ENOSPC.  Consumed by that encode.  Host state only.
+ * Returns 0, or -2 on bad arguments. */
+int mij_test_sampled_out_cap(mij_batch *b, int frame, long long cap);
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,10 @@
  * input convention is BGR888 (encoder.c:133), so channels are swapped on load.
  *
  *   encode_ppm <in.ppm> <out.jpg> [quality] [x y w h] [--fused]
+ *   encode_ppm <in.ppm> <out.jpg> [quality] --sampling 444|422|420|gray
+ *
+ * With --sampling the PPM may have any size and becomes one standard
+ * interleaved baseline stream at that chroma sampling (mij_encode_sampled).
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -16,7 +20,7 @@
 
 #include "mijpeg.h"
 
-static uint8_t *read_ppm_bgr(const char *path, int *w, int *h) {
+static uint8_t *read_ppm_bgr(const char *path, int *w, int *h, int any_size) {
     FILE *f = fopen(path, "rb");
     if (!f) { perror(path); return NULL; }
     char magic[3] = {0};
@@ -36,8 +40,8 @@ static uint8_t *read_ppm_bgr(const char *path, int *w, int *h) {
         n++;
     }
     fgetc(f); /* single whitespace after the depth */
-    if (n != 3 || vals[2] != 255 || vals[0] % 16 || vals[1] % 16 || vals[0] <= 0 || vals[1] <= 0) {
-        fprintf(stderr, "%s: need depth 255 and dimensions multiple of 16\n", path);
+    if (n != 3 || vals[2] != 255 || vals[0] <= 0 || vals[1] <= 0 || (!any_size && (vals[0] % 16 || vals[1] % 16))) {
+        fprintf(stderr, "%s: need depth 255 and dimensions %s\n", path, any_size ? "above 0" : "multiple of 16");
         fclose(f);
         return NULL;
     }
@@ -58,15 +62,44 @@ static uint8_t *read_ppm_bgr(const char *path, int *w, int *h) {
 
 int main(int argc, char **argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: %s <in.ppm> <out.jpg> [quality] [x y w h] [--fused]\n", argv[0]);
+        fprintf(stderr, "usage: %s <in.ppm> <out.jpg> [quality] [x y w h] [--fused]\n"
+                        "       %s <in.ppm> <out.jpg> [quality] --sampling 444|422|420|gray\n", argv[0], argv[0]);
         return 2;
     }
-    int fused = 0;
+    int fused = 0, sampling = -1;
+    for (int i = 3; i + 1 < argc; i++)
+        if (!strcmp(argv[i], "--sampling")) { /* the option and its value leave the argument list */
+            static const char *const names[4] = {"420", "422", "444", "gray"};
+            for (int k = 0; k < 4; k++)
+                if (!strcmp(argv[i + 1], names[k])) sampling = k;
+            if (sampling < 0) {
+                fprintf(stderr, "--sampling %s: one of 444, 422, 420, gray\n", argv[i + 1]);
+                return 2;
+            }
+            for (int j = i; j + 2 < argc; j++) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
     if (!strcmp(argv[argc - 1], "--fused")) { fused = 1; argc--; }
     int W, H;
-    uint8_t *raw = read_ppm_bgr(argv[1], &W, &H);
+    uint8_t *raw = read_ppm_bgr(argv[1], &W, &H, sampling >= 0);
     if (!raw) return 1;
     int quality = argc > 3 ? atoi(argv[3]) : 50;
+    if (sampling >= 0) {
+        size_t bound = mij_max_jpg_bytes_sampled(W, H, sampling, 0), n = 0;
+        uint8_t *out = malloc(bound ? bound : 1);
+        if (!out || mij_encode_sampled(raw, W, W, H, MIJ_PIX_BGR, quality, sampling, 0, out, bound, &n) != MIJ_OK) {
+            fprintf(stderr, "%s: %s\n", argv[1], mij_last_message());
+            return 1;
+        }
+        FILE *f = fopen(argv[2], "wb");
+        if (!f || fwrite(out, 1, n, f) != n) { perror(argv[2]); return 1; }
+        fclose(f);
+        printf("%s: %dx%d Q=%d sampling %d -> %zu bytes\n", argv[2], W, H, quality, sampling, n);
+        free(raw);
+        free(out);
+        return 0;
+    }
     area_t dims = {0, 0, W, H};
     if (argc > 7) { dims.x = atoi(argv[4]); dims.y = atoi(argv[5]); dims.w = atoi(argv[6]); dims.h = atoi(argv[7]); }
     size_t cap = mij_max_jpg_bytes(dims.w, dims.h);

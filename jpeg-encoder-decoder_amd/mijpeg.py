@@ -53,6 +53,8 @@ EXPORTS = [
     "mij_transcode",
     "mij_decoder_transform", "mij_transform", "mij_exif_orientation", "mij_orientation_op",
     "mij_decoder_reconstruct_scaled", "mij_decoder_scaled_layout", "mij_decode_scaled",
+    "mij_max_jpg_bytes_sampled", "mij_batch_encode_sampled", "mij_batch_sampled_component",
+    "mij_batch_sampled_layout", "mij_encode_sampled",
 ]
 
 
@@ -255,6 +257,12 @@ def load() -> C.CDLL:
         lib.mij_decoder_reconstruct_scaled.argtypes = [p, i, i]
         lib.mij_decoder_scaled_layout.argtypes = [p, i, i, p, i]
         lib.mij_decode_scaled.argtypes = [p, sz, i, i, p, sz, C.POINTER(i), C.POINTER(i)]
+        lib.mij_max_jpg_bytes_sampled.restype = sz
+        lib.mij_max_jpg_bytes_sampled.argtypes = [i, i, i, i]
+        lib.mij_batch_encode_sampled.argtypes = [p, i, i, i]
+        lib.mij_batch_sampled_component.argtypes = [p, i, i, p, sz]
+        lib.mij_batch_sampled_layout.argtypes = [p, i, p, i]
+        lib.mij_encode_sampled.argtypes = [p, i, i, i, i, i, i, i, p, sz, C.POINTER(sz)]
     except AttributeError:
         if not os.environ.get("MIJ_LIB"):  # older builds only in A/B timing runs
             raise
@@ -380,19 +388,42 @@ def max_jpg_bytes_any(w: int, h: int, restart_rows: int = 0) -> int:
     return int(load().mij_max_jpg_bytes_any(w, h, restart_rows))
 
 
-def encode_any(frame: np.ndarray, order: str = "bgr", quality: int = 50, restart_rows: int = 0) -> bytes:
+SAMPLINGS = {"420": 0, "422": 1, "444": 2, "gray": 3}  # MIJ_SAMP_*
+
+
+def _sampling(sampling) -> int:
+    if sampling not in SAMPLINGS:
+        raise ValueError(f"sampling {sampling!r}: one of {sorted(SAMPLINGS)}")
+    return SAMPLINGS[sampling]
+
+
+def max_jpg_bytes_sampled(w: int, h: int, sampling: str = "420", restart_rows: int = 0) -> int:
+    return int(load().mij_max_jpg_bytes_sampled(w, h, _sampling(sampling), restart_rows))
+
+
+def encode_any(frame: np.ndarray, order: str = "bgr", quality: int = 50, restart_rows: int = 0,
+               sampling: str = "420") -> bytes:
     """mij_encode_any: an (h, w, 3) frame of any size to a standard
-    interleaved baseline stream, host to host."""
+    interleaved baseline stream, host to host; with sampling
+    "422", "444" or "gray" through mij_encode_sampled."""
     lib = load()
     frame = np.ascontiguousarray(frame, np.uint8)
     h, w = frame.shape[:2]
     n = C.c_size_t(0)
-    rc = lib.mij_encode_any(None, w, w, h, PIXEL_ORDERS[order], quality, restart_rows, None, 0, C.byref(n))
+    if _sampling(sampling):
+        def call(px, out, cap):
+            return lib.mij_encode_sampled(px, w, w, h, PIXEL_ORDERS[order], quality, SAMPLINGS[sampling],
+                                          restart_rows, out, cap, C.byref(n))
+        what = "mij_encode_sampled"
+    else:
+        def call(px, out, cap):
+            return lib.mij_encode_any(px, w, w, h, PIXEL_ORDERS[order], quality, restart_rows, out, cap, C.byref(n))
+        what = "mij_encode_any"
+    rc = call(None, None, 0)
     if rc != 4:  # MIJ_ENOSPC carries the bound
-        _check(rc or 1, "mij_encode_any")
+        _check(rc or 1, what)
     out = np.zeros(n.value, np.uint8)
-    _check(lib.mij_encode_any(_ptr(frame), w, w, h, PIXEL_ORDERS[order], quality, restart_rows, _ptr(out),
-                              out.size, C.byref(n)), "mij_encode_any")
+    _check(call(_ptr(frame), _ptr(out), out.size), what)
     return out[:n.value].tobytes()
 
 
@@ -492,6 +523,29 @@ class Batch:
         """slots 0..n-1 (padded input) to one-interleaved-scan streams of
         their true sizes; restart_rows MCU rows per restart interval (0: none)"""
         _check(self.lib.mij_batch_encode_interleaved(self.h_, n, restart_rows), "encode_interleaved")
+
+    def encode_sampled(self, n: int, sampling: str = "444", restart_rows: int = 0) -> None:
+        """encode_interleaved at a chroma sampling ("420", "422", "444", "gray";
+        mij_batch_encode_sampled); restart_rows counts MCU rows of that sampling"""
+        _check(self.lib.mij_batch_encode_sampled(self.h_, n, _sampling(sampling), restart_rows), "encode_sampled")
+
+    def sampled_layout(self, frame: int) -> dict:
+        """mij_batch_sampled_layout: the geometry the last encode_sampled coded, as Decoder.layout gives it"""
+        out = np.zeros(24, np.int32)
+        _check(self.lib.mij_batch_sampled_layout(self.h_, frame, _ptr(out), out.size), "sampled_layout")
+        v = [int(x) for x in out]
+        keys = ("w", "h", "ncomp", "hmax", "vmax", "mcus_x", "mcus_y", "ri", "interleaved")
+        lay = dict(zip(keys, v[:9]))
+        lay["comps"] = [tuple(v[9 + 5 * c:14 + 5 * c]) for c in range(lay["ncomp"])]  # h, v, tq, bw, bh
+        lay["raw"] = v[:9 + 5 * lay["ncomp"]]
+        return lay
+
+    def sampled_component(self, frame: int, comp: int) -> np.ndarray:
+        """(blocks, 64) int16: the plane the last encode_sampled coded, zigzag order, absolute DC"""
+        _, _, _, bw, bh = self.sampled_layout(frame)["comps"][comp]
+        out = np.zeros((bw * bh, 64), np.int16)
+        _check(self.lib.mij_batch_sampled_component(self.h_, frame, comp, _ptr(out), out.size), "sampled_component")
+        return out
 
     def upload(self, frames_bgr: np.ndarray, first: int = 0) -> None:
         frames_bgr = np.ascontiguousarray(frames_bgr, np.uint8)
