@@ -211,8 +211,10 @@ int mij_batch_stage_ms(mij_batch *b, float *ms, int n);
 /* the same for each of the last `steps` encodes (<= 64) issued while timing
  * was on, oldest first: ms[step*MIJ_NSTAGES + stage]; returns the count filled */
 int mij_batch_stage_history(mij_batch *b, float *ms, int steps);
-/* symbol tokens K1 emitted for the last encode of nframes frames (4 bytes
- * each; used for the bandwidth accounting of the fused kernel) */
+/* symbol tokens K1 stored in the token buffer for the last encode of nframes
+ * frames (4 bytes each; used for the bandwidth accounting of the fused
+ * kernel).  DC-only chroma segments, whose tokens the packing builds from the
+ * raw DCs instead of a stored stream, add nothing to it. */
 unsigned long long mij_batch_token_count(mij_batch *b, int nframes);
 /* {w, h, 8x8 blocks per frame, segments per frame, K1 tiles per frame,
  *  the pack kernel's LDS window in words at the batch's quality}: the first n */

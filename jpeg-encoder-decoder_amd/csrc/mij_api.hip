@@ -778,7 +778,7 @@ static EntArgs ent_args(mij_batch *b, int nframes, int f0 = 0, bool band = false
 // mode: K1 mode bits (1 coefficient planes out, 2 tokens + histograms out,
 // 4 coefficient planes in)
 static int run_k1(mij_batch *b, int nframes, int mode, int dc_diffed = 0, int seg_dc_inline = 0, int f0 = 0,
-                  bool stage_events = true) {
+                  bool stage_events = true, bool dc_only = false) {
   // a token-emitting K1 (modes 2, 3, 6: the band calls too) adds onto d_hist:
   // the next encode must zero it again
   if (mode & 2) b->hist_zero_n = b->band_hist_zero = 0;
@@ -839,7 +839,9 @@ static int run_k1(mij_batch *b, int nframes, int mode, int dc_diffed = 0, int se
     HIP_TRY(hipMemsetAsync(d_wt, 0, sizeof(unsigned long long) * K1_WTIME_WORDS * nw, b->stream));
     k.wtime = d_wt;
   }
+  k.dc_only = dc_only;
   b->plan[MIJ_PLAN_K1_MODE] = mode;
+  b->plan[MIJ_PLAN_DC_ONLY] = dc_only;
   HIP_TRY(launch_k1(k, (int)grid, mode, b->stream));
   if (d_wt) {
     const int WW = K1_WTIME_WORDS;
@@ -1102,6 +1104,14 @@ static int encode_frames(mij_batch *b, int nframes) {
   // a memset launch is 4-5 us of a one-frame step)
   b->k1_err_zero = nframes;
   if (b->timing) HIP_TRY(hipEventRecord(b->ev[0], b->stream));
+  // DC-only chroma segments keep no token stream (K1Args::dc_only; the pack
+  // builds their tokens from the raw DCs): whole-canvas batches from pixels in
+  // the fused pipeline, sub-batches included.  Off for region batches, the
+  // split pipeline and the qualities of the wide pack window (K1's
+  // all-AC-zero test is off long before them, and that k_pack_flat variant is
+  // compiled without the DC-only path); the band, assembler and
+  // coefficient-input paths launch their own K1s and never set it.
+  const bool dc_only = !b->split && !b->use_fdims && !ent_args_pack_wide(b);
   const int nsub = std::min(b->overlap, nframes);
   if (!b->split && !b->keep_coefs && nsub > 1) {
     // sub-batches: K1 of sub-batch k on the batch stream, its entropy stages
@@ -1110,7 +1120,7 @@ static int encode_frames(mij_batch *b, int nframes) {
     const int per = (nframes + nsub - 1) / nsub;
     for (int k = 0, f0 = 0; f0 < nframes; k++, f0 += per) {
       const int nk = std::min(per, nframes - f0);
-      if (run_k1(b, nk, 2, 0, 0, f0, false)) return g_err;
+      if (run_k1(b, nk, 2, 0, 0, f0, false, dc_only)) return g_err;
       HIP_TRY(hipEventRecord(b->ov_k1[k], b->stream));
       HIP_TRY(hipStreamWaitEvent(b->stream2, b->ov_k1[k], 0));
       if (run_entropy(b, nk, true, false, f0, b->stream2)) return g_err;
@@ -1127,7 +1137,7 @@ static int encode_frames(mij_batch *b, int nframes) {
     if (run_k1(b, nframes, 1)) return g_err;  // records events 1 and 2 around the fixer
     if (run_k1(b, nframes, 6, 0, 1)) return g_err;  // segment-first DCs inline: no k_seg_dc
   } else {
-    if (run_k1(b, nframes, b->keep_coefs ? 3 : 2)) return g_err;  // events 1 and 2 (no fixer)
+    if (run_k1(b, nframes, b->keep_coefs ? 3 : 2, 0, 0, 0, true, dc_only)) return g_err;  // events 1 and 2 (no fixer)
   }
   if (b->timing) HIP_TRY(hipEventRecord(b->ev[3], b->stream));
   if (run_entropy(b, nframes, !b->split, false)) return g_err;
@@ -1444,7 +1454,7 @@ extern "C" unsigned long long mij_batch_token_count(mij_batch *b, int nframes) {
       hipSuccess)
     return 0;
   unsigned long long n = 0;
-  for (uint32_t x : v) n += x;
+  for (uint32_t x : v) n += x >> 31 ? 0u : x;  // (bit 31, SEG_DC_ONLY: no stream stored)
   return n;
 }
 

@@ -173,7 +173,7 @@ struct K1Args {
   const int16_t *dc_pred;   // coefficient input, inline: DC predictor per frame [4] (null: 0)
   uint32_t *tok;            // token mode: per segment SEG_TOK tokens (token 0 in tok0)
   uint32_t *tok0;           // token mode: per segment its first token (the first block's DC)
-  uint32_t *seg_ntok;       // token mode: tokens per segment
+  uint32_t *seg_ntok;       // token mode: tokens per segment (bit 31: SEG_DC_ONLY)
   uint32_t *hist;           // token mode: per frame [4][257] histograms
   // coefficient mode: per K1 N-tile (global tile * 3 + nt) the 16-bit mask of
   // its blocks k_fix_blocks must recompute; all zero between launches (K1
@@ -187,6 +187,8 @@ struct K1Args {
                             // straddle bits of zigzag 16g..16g+15; null in every product launch
   int *err_zero;            // an encode's first K1: workgroup 0 zeroes these per-frame error
   int nerr_zero;            // words (k_tables on write them), instead of a memset launch
+  int dc_only;              // token mode from pixels: an all-AC-zero chroma N-tile stores no tokens,
+                            // only seg_ntok = SEG_DC_ONLY | count (the readers build them from dc)
 };
 constexpr int K1_WTIME_WORDS = 8;
 // K1 diagnostic switches (timing attribution; outputs are wrong when set)
@@ -209,7 +211,7 @@ struct EntArgs {
   const uint32_t *ehuf;     // per frame [4][256] = len << 16 | code
   uint32_t *tok;            // per segment SEG_TOK tokens (token 0 in tok0)
   uint32_t *tok0;           // per segment its first token
-  const uint32_t *seg_ntok; // per segment token count
+  const uint32_t *seg_ntok; // per segment token count (bit 31: SEG_DC_ONLY, no stream stored)
   uint32_t *seg_bits;       // per segment bits
   uint64_t *seg_off;        // per segment bit offset inside its scan
   uint64_t *scan_bits;      // per frame [3]

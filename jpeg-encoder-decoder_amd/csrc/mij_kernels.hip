@@ -561,6 +561,9 @@ constexpr uint32_t TOK_AC = 1u << 10;
 // token carries: magnitudes stop at class 11): the packing's code table holds
 // 0 for it -- no bits, no ZRLs
 constexpr uint32_t LB_NOTOK = TOK_AC | 0xFFu;
+// seg_ntok, bit 31: a DC-only segment without a token stream (every block is
+// its DC difference and EOB); the low bits stay its token count, 2 per block
+constexpr uint32_t SEG_DC_ONLY = 1u << 31;
 
 // One N-tile of coefficients -> compacted token stream of its segment(s).
 // o[k] = zigzag coefficient 16g+k of block bcol (DC raw in o[0] of g == 0,
@@ -582,10 +585,28 @@ __device__ __forceinline__ void emit_tokens(const int (&o)[16], int lane, int g,
                                             bool valid, bool chroma, bool dc_diffed,
                                             bool first_pred, int pred0,
                                             uint32_t *segtok, uint32_t segoff, uint32_t *tok0, uint32_t *segcnt, uint32_t *hDC,
-                                            uint32_t *hAC, int16_t (*st)[16], int kflags = 0, bool acz = false) {
+                                            uint32_t *hAC, int16_t (*st)[16], int kflags = 0, bool acz = false, bool dc_only = false) {
   // acz (a compile-time constant where it is set): every AC coefficient of
   // the N-tile is zero -- no staging, no masks, no AC tokens; each block is
   // its DC token and EOB
+  // dc_only (K1Args::dc_only, with acz, chroma): the segment keeps no token
+  // stream at all.  Its tokens are "DC difference, EOB" per block, a function
+  // of the raw DCs K1 stores anyway, so the entropy stages build them from
+  // those (seg_chunk): the count alone goes out, flagged SEG_DC_ONLY, and the
+  // histograms get what the tokens would have added -- the DC classes of
+  // every block but the segment's first (k_seg_dc's, as always) and the EOBs.
+  if (acz && dc_only) {
+    const int dc0 = o[0];
+    const int prev = (int)row_shr0<1>((uint32_t)dc0);
+    const unsigned long long vb = __ballot(valid && g == 0);  // Cb and Cr hold the same columns
+    if (g == 0) {
+      // tokens per segment: 2 per valid block, popc(vb) over both halves
+      if ((bcol & 7) == 7) *segcnt = SEG_DC_ONLY | (uint32_t)__popcll(vb);
+      if (valid && (bcol & 7) != 0) atomicAdd(&hDC[mag_class(dc0 - prev)], 1u);
+    }
+    if (lane == 0 && vb) atomicAdd(&hAC[0x00], (unsigned)__popcll(vb));
+    return;
+  }
   uint32_t Mlo = 0, Mhi = 0;
   const int zsw = 8 * (bcol & 7);
   if (!acz) {
@@ -1159,7 +1180,7 @@ __global__ __launch_bounds__(64 * k1_waves<MODE>(), k1_wide<MODE>() ? 1 : 2) voi
                       a.tok + (long long)p.f * G.nseg * SEG_TOK, (uint32_t)seg * SEG_TOK, a.tok0 + fs,
                       a.seg_ntok + fs, s_hdc[TOK ? slot : 0][comp][bcol & (HREP - 1)],
                       s_hac[TOK ? slot : 0][comp][bcol & (HREP - 1)],
-                      s_st[TOK ? wave : 0], kflags, acz);
+                      s_st[TOK ? wave : 0], kflags, acz, PIX && !REG && a.dc_only);
         }
       };
       if (FLOOR) {
@@ -1217,7 +1238,19 @@ __global__ __launch_bounds__(64 * k1_waves<MODE>(), k1_wide<MODE>() ? 1 : 2) voi
                   all &= lo & ~hi;
                 }
               }
-              if (!__ballot((int)all >= 0)) {
+              bool fails = (int)all >= 0;
+              if constexpr (TOK) {
+                // token variants: columns past the frame's right edge hold
+                // whatever pixels the wave's staging held before -- they do
+                // not vote, so which segments are DC-only depends on the
+                // frame alone.  (asm volatile: the column is computed here,
+                // one v_and; hoisted out of the tile loop it costs a VGPR the
+                // kernel does not have)
+                uint32_t ccol;
+                asm volatile("v_and_b32 %0, 7, %1" : "=v"(ccol) : "v"(lane));
+                fails = fails && (int)ccol < (p.valid_px >> 4);
+              }
+              if (!__ballot(fails)) {
 #pragma unroll
                 for (int k = 0; k < 16; k++) o[k] = 0;
                 bool tie;
@@ -1648,6 +1681,39 @@ __device__ __forceinline__ bool seg_info(const Geom &G, const FGeom &fg, int s, 
   const int r = (int)div_by((uint32_t)local, G.tx_m, G.tx_s), tx = local - r * G.tiles_x;
   first = cstart + r * fg.mw + tx * 8;
   return r < fg.rows && tx < fg.tiles_x;
+}
+
+// Chunk j of a segment's token stream: its tokens 4j .. 4j + 3, the one way
+// the entropy stages read tokens (k_pack_flat, k_seg_bits).  A stored stream
+// comes from the segment's slot, padded by K1 to a multiple of 4 with
+// LB_NOTOK.  A SEG_DC_ONLY segment (dc_only) has no stream: block i is tokens
+// 2i (its DC difference, encoder.c:168-177, :434-446) and 2i + 1 (EOB,
+// :479-484), built from the raw DCs of blocks 2j - 1 .. 2j + 1 of the segment,
+// whose first block index is the segment geometry's (seg_info); slots past
+// the count read LB_NOTOK (tail: the count is no multiple of 4 -- an odd block
+// count, a right-edge tile -- so the last chunk ends in two of them).  Token 0
+// is the dense tok0 entry either way.  (fs = f * nseg + s.)
+__device__ __forceinline__ u4v seg_chunk(const EntArgs &a, int f, int s, long long fs, uint32_t j, bool dc_only,
+                                         bool tail) {
+  u4v t;
+  if (dc_only) {
+    // (K1 flags segments in whole-canvas batches only: no per-frame sizes)
+    const FGeom fg = frame_geom(a.g, nullptr, f);
+    int comp, first, cstart, local;
+    seg_info(a.g, fg, s, comp, first, cstart, local);
+    const int16_t *dc = a.dc + (long long)f * a.g.nblk + first + 2 * (int)j;
+    const bool two = !tail || 4u * j + 2u < (a.seg_ntok[fs] & ~SEG_DC_ONLY);
+    const int d0 = dc[0], dp = j ? (int)dc[-1] : 0, d1 = two ? (int)dc[1] : 0;
+    const int c0 = mag_class(d0 - dp), c1 = mag_class(d1 - d0);
+    t[0] = j ? (uint32_t)c0 | (mag_bits(d0 - dp, c0) << 16) : a.tok0[fs];
+    t[1] = TOK_AC;
+    t[2] = two ? (uint32_t)c1 | (mag_bits(d1 - d0, c1) << 16) : LB_NOTOK;
+    t[3] = two ? TOK_AC : LB_NOTOK;
+    return t;
+  }
+  t = *(const u4v *)(a.tok + fs * SEG_TOK + 4u * j);
+  if (j == 0) t[0] = a.tok0[fs];
+  return t;
 }
 
 // ===========================================================================
@@ -2767,22 +2833,24 @@ __global__ __launch_bounds__(256) void k_seg_bits(EntArgs a) {
   const int send = min(s0 + SEG_PER_WG, a.g.nseg);
   for (int s = s0 + grp; s < send; s += 16) {
     const long long fs = (long long)f * a.g.nseg + s;
-    const int n = min((int)a.seg_ntok[fs], SEG_TOK);
-    const uint32_t *tk = a.tok + fs * SEG_TOK;
-    const uint32_t tz = a.tok0[fs];  // token 0
+    const uint32_t ntw = a.seg_ntok[fs];
+    const bool dco = (ntw & SEG_DC_ONLY) != 0;
+    const int n = min((int)(ntw & ~SEG_DC_ONLY), SEG_TOK);
     const int chroma = s >= a.g.nsy;
     uint32_t b = 0;
-    // four loads in flight per lane before any is used (latency-bound loop)
-    for (int i0 = 0; i0 < n; i0 += 64) {
-      uint32_t t[4];
+    // four chunk loads in flight per lane before any is used (latency-bound loop)
+    for (int j0 = 0; 4 * j0 < n; j0 += 64) {
+      u4v t[4];
 #pragma unroll
       for (int u = 0; u < 4; u++) {
-        const int i = i0 + 16 * u + sub;
-        t[u] = i < n ? (i ? tk[i] : tz) : 0u;
+        const int j = j0 + 16 * u + sub;
+        t[u] = 4 * j < n ? seg_chunk(a, f, s, fs, (uint32_t)j, dco, (n & 3) != 0) : u4v{0u, 0u, 0u, 0u};
       }
 #pragma unroll
       for (int u = 0; u < 4; u++)
-        if (i0 + 16 * u + sub < n) b += tok_bits(t[u], tab, chroma);
+#pragma unroll
+        for (int e = 0; e < 4; e++)
+          if (4 * (j0 + 16 * u + sub) + e < n) b += tok_bits(t[u][e], tab, chroma);
     }
     b = row_scan16(b);
     if (sub == 15) a.seg_bits[fs] = b;
@@ -3044,7 +3112,7 @@ __global__ __launch_bounds__(PF_THREADS, pf_occ<PW>()) void k_pack_flat(EntArgs 
   auto seg_count = [&](int qq) -> uint32_t {
     const int s0q = qq * pseg, nsq = min(ns, s0q + pseg) - s0q;
     return tid < nsq ? a.seg_ntok[(long long)f * G.nseg + sbase + s0q + tid] : 0u;
-  };
+  };  // (with its SEG_DC_ONLY bit)
   const uint32_t nt_guess = seg_count(qg);
   if (tid == 0) s_ticket = (int)atomicAdd(&a.pack_ticket[f * 3 + comp], 1u);
   tab[tid] = lb_tab_entry(e0, (uint32_t)tid);
@@ -3065,7 +3133,8 @@ __global__ __launch_bounds__(PF_THREADS, pf_occ<PW>()) void k_pack_flat(EntArgs 
   const int s0 = q * pseg, nsg = min(ns, s0 + pseg) - s0;
   const long long fs0 = (long long)f * G.nseg + sbase + s0;  // the group's first segment
   {  // chunks per segment (K1 padded each to a multiple of 4 tokens), a thread per segment
-    const uint32_t nt = min(q == qg ? nt_guess : seg_count(q), (uint32_t)SEG_TOK);
+    const uint32_t ntw = q == qg ? nt_guess : seg_count(q);
+    const uint32_t nt = min(ntw & ~SEG_DC_ONLY, (uint32_t)SEG_TOK);
     const uint32_t ch = (nt + 3u) >> 2;
     const uint32_t incl = wave_scan64(ch);
     if (lane == 63) s_wt[wave] = incl;
@@ -3077,11 +3146,14 @@ __global__ __launch_bounds__(PF_THREADS, pf_occ<PW>()) void k_pack_flat(EntArgs 
       tot += v;
       before += w < wave ? v : 0u;
     }
-    s_cp[tid] = tid < nsg ? before + incl - ch : 0xFFFFFFFFu;  // (no chunk maps past the group)
-    if (tid == 0) s_cp[PACK_SEGS_MAX] = tot;
+    // s_cp: 4 x the prefix, + 1 for a SEG_DC_ONLY segment (its chunks come from
+    // the raw DCs: seg_chunk), + 2 when its count is no multiple of 4 -- prefix
+    // p <= chunk c iff 4 p + flags <= 4 c + 3
+    s_cp[tid] = tid < nsg ? 4u * (before + incl - ch) + (ntw >> 31) + (nt & 3u ? 2u : 0u) : 0xFFFFFFFFu;  // (no chunk maps past the group)
+    if (tid == 0) s_cp[PACK_SEGS_MAX] = 4u * tot;
   }
   __syncthreads();
-  const uint32_t C = s_cp[PACK_SEGS_MAX];
+  const uint32_t C = s_cp[PACK_SEGS_MAX] >> 2;
   PF_STAMP(1);
   // The window is zeroed as far as the group can need it at <= 96 bits per
   // chunk (3C + 2 words: a chroma group of ~256 chunks zeroes ~770 words, not
@@ -3091,19 +3163,20 @@ __global__ __launch_bounds__(PF_THREADS, pf_occ<PW>()) void k_pack_flat(EntArgs 
   // the sweep's first barrier orders them before any placement.
   const uint32_t wz = min((uint32_t)PW, (3u * C + 2u + 3u) & ~3u);
   for (uint32_t i = 4u * tid; i < wz; i += 4u * PF_THREADS) *(u4v *)&buf[i] = u4v{0u, 0u, 0u, 0u};
-  const uint32_t *tokg = a.tok + fs0 * SEG_TOK;
-  // chunk c's 4 tokens (c < C): its segment s is the last with s_cp[s] <= c
+  // chunk c's 4 tokens (c < C): its segment s is the last with prefix <= c
   auto chunk_seg = [&](uint32_t c) -> int {
     int s = 0;
+    const uint32_t c2 = 4u * c + 3u;
 #pragma unroll
     for (int step = PACK_SEGS_MAX / 2; step; step >>= 1)  // (entries past the group read ~0)
-      if (s_cp[s + step] <= c) s += step;
+      if (s_cp[s + step] <= c2) s += step;
     return s;
   };
   auto chunk_at = [&](uint32_t c, int s, u4v &t) {
-    const uint32_t o = 4u * (c - s_cp[s]);
-    t = *(const u4v *)(tokg + (long long)s * SEG_TOK + o);
-    if (o == 0) t[0] = a.tok0[fs0 + s];  // token 0 of a segment (dense array)
+    const uint32_t cp = s_cp[s];
+    // (the wide window runs at qualities where K1's all-AC-zero test is off and
+    // the host leaves dc_only off: no DC-only path in that variant)
+    t = seg_chunk(a, f, sbase + s0 + s, fs0 + s, c - (cp >> 2), PW == PACK_WORDS && (cp & 1u) != 0, (cp & 2u) != 0);
   };
   auto chunk_load = [&](uint32_t c, u4v &t) {
     t = u4v{0u, 0u, 0u, 0u};
@@ -3122,7 +3195,7 @@ __global__ __launch_bounds__(PF_THREADS, pf_occ<PW>()) void k_pack_flat(EntArgs 
 #pragma unroll
     for (int k = 1; k < K; k++) {
       if (c + k >= C) break;
-      while (s_cp[s + 1] <= c + k) s++;
+      while (s_cp[s + 1] <= 4u * (c + k) + 3u) s++;
       chunk_at(c + k, s, t[k]);
     }
   };

@@ -41,6 +41,9 @@ enum {
   MIJ_PLAN_HIST_FILL_SKIPPED, /* the histogram fill before K1 was skipped */
   MIJ_PLAN_K1_MODE,         /* mode bits of the last K1 launch (2 tokens, 3 tokens +
                                coefficient planes, 6 tokens from the planes: split) */
+  MIJ_PLAN_DC_ONLY,         /* that K1 stored no token stream for all-AC-zero chroma
+                               segments (seg_ntok bit 31; the pack builds their tokens
+                               from the raw DCs) */
   MIJ_PLAN_FIELDS
 };
 int mij_test_last_plan(mij_batch *b, int *out, int n);

@@ -88,7 +88,7 @@ OPTIONS = {"seam": 0, "ff_pack": 1, "actab": 2, "segdc_fused": 3, "pack_wide": 4
 # mij_test_last_plan (csrc/mij_testing.h: MIJ_PLAN_*), in the library's order
 PLAN_FIELDS = ["nframes", "f0", "entropy_calls", "dc_last", "actab", "tables", "segdc", "seam", "ff_pack",
                "seam_in_scan", "emit_slots", "pack_ls_luma", "pack_ls_chroma", "pack_wide",
-               "hist_fill_skipped", "k1_mode"]
+               "hist_fill_skipped", "k1_mode", "dc_only"]
 
 
 _lib = None
