@@ -596,9 +596,12 @@ void *mij_decoder_device_coefs(mij_decoder *d, int frame);
  * component ids, restart intervals.  Such a frame's planes are padded to
  * whole MCUs; mij_decoder_coefs / _planes are defined as the encoder's layout
  * and return MIJ_EINVAL on it: use the three calls below, which work on
- * every frame.  The memory for such frames is allocated when a decode call
- * first holds one and grows (is freed and allocated again) when a call needs
- * more; a decoder that only sees the encoder's streams allocates none.
+ * every frame.  All frames of a call share one set of device buffers, packed
+ * in the order of the call.  Each buffer's first allocation takes what
+ * max_frames frames of max_w x max_h of the encoder's shape need (the
+ * coefficients' at mij_decoder_create, the others' at first use) and grows
+ * (is freed and allocated again) only when a call's padded planes need more;
+ * a decoder that only sees the encoder's streams never reallocates.
  *
  * layout: out[0..8] = w, h, components, max H, max V, MCUs across, MCUs
  * down, restart interval (0 = none), 1 if one interleaved scan; then per

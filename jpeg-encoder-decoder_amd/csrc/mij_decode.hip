@@ -13,8 +13,9 @@
 // one interleaved scan (a greyscale file's single scan included), greyscale
 // or YCbCr with luma 1x1 / 2x1 / 2x2 and chroma 1x1, any size from 1x1,
 // arbitrary component ids, DQT ids 0..3, restart intervals.  Their planes are
-// padded to whole MCUs and live in an arena of their own (k_il_* kernels;
-// DESIGN.md "Decoding ordinary baseline files").  Refused with MIJ_EJPEG and
+// padded to whole MCUs.  Both shapes go through the same kernels and share
+// one arena: a one-component scan is an interleaved scan whose MCU is one
+// block (DESIGN.md "Decoding ordinary baseline files").  Refused with MIJ_EJPEG and
 // the reason: SOF1..15, 12-bit samples, 16-bit DQT, 2 or 4 components, Adobe
 // RGB / YCCK, other sampling, further scans, Ss/Se/AhAl other than 0/63/0,
 // missing tables, restart markers missing or out of order.
@@ -60,15 +61,6 @@ struct DecTab {
   int32_t maxcode[18];       // largest code of each length, -1 if none
   int32_t valoff[17];        // index of the first symbol of a length - its code
   uint8_t val[256];
-};
-
-struct DecJob {
-  long long data;   // byte offset of the UNSTUFFED scan in the blob (8-aligned)
-  long long nbits;  // its length in bits (the pad bits included)
-  long long out;    // first int16 of the component's plane
-  int nblocks;
-  int dc, ac;       // table indices
-  int chunk0, nchunks;  // global ids of the scan's chunks
 };
 
 // chunk c of a scan covers bits [c*CHUNK, (c+1)*CHUNK): a symbol belongs to
@@ -130,443 +122,69 @@ __device__ __forceinline__ int decode_one(Bits &br, long long pos, const DecTab 
   return len + s;
 }
 
-// Decodes from (pos, k) until pos reaches `stop` or `blocks_left` blocks
-// have ended.  k = next coefficient index (0 = a DC symbol is next).
-// Returns the number of blocks started; pos/k are the state after the last
-// symbol.  WRITE: coefficients go to out[64*blk + zigzag index] (nonzeros
-// only; the planes are zeroed first).  *bad = invalid code met.
-template <bool WRITE>
-__device__ int decode_span(Bits &br, long long &pos, int &k, long long stop, const DecTab &dc,
-                           const DecTab &ac, int16_t *out, long long blk, long long blocks_left,
-                           bool *bad) {
-  int started = 0;
-  *bad = false;
-  while (pos < stop) {
-    int sym, val;
-    if (k == 0) {
-      if (blocks_left <= 0) break;
-      const int n = decode_one(br, pos, dc, sym, val);
-      if (!n || sym > 15) {
-        *bad = true;
-        break;
-      }
-      pos += n;
-      if (WRITE && val) out[64 * blk] = (int16_t)val;
-      started++;
-      k = 1;
-    } else {
-      const int n = decode_one(br, pos, ac, sym, val);
-      if (!n) {
-        *bad = true;
-        break;
-      }
-      pos += n;
-      const int r = sym >> 4;
-      if (sym & 15) {
-        k += r;
-        if (k > 63) {
-          *bad = true;
-          break;
-        }
-        if (WRITE) out[64 * blk + k] = (int16_t)val;
-        k++;
-      } else if (r == 15) {
-        k += 16;  // ZRL
-      } else {
-        k = 64;   // EOB
-      }
-    }
-    if (k >= 64) {
-      k = 0;
-      blk++;
-      blocks_left--;
-    }
-  }
-  return started;
-}
-
-__device__ __forceinline__ int job_of(const DecJob *jobs, int njobs, int c) {
-  int lo = 0, hi = njobs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (jobs[mid].chunk0 <= c) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-// Self-synchronising pass (Weissenberger & Schmidt, ICPP 2018): chunk c
-// decodes from its entry state to its end.  First pass: every chunk starts
-// at its first bit as if a block began there (exact for chunk 0 of a
-// scan).  Later passes: the entry of chunk c is the exit of chunk c-1 from
-// the previous pass; a chunk whose entry did not change keeps its result.
-// Huffman streams resynchronise within a few symbols, so 2-3 passes settle.
-struct SyncArgs {
-  const uint8_t *blob;
-  const DecJob *jobs;
-  int njobs, nchunks;
-  const DecTab *tabs;
-  long long *entry_pos, *exit_in, *exit_out;  // pos * 64 + k packed
-  int *nblk;
-  int *changed;
-  int first;
-};
-
-__device__ __forceinline__ long long pack_state(long long pos, int k) { return pos * 64 + k; }
-
-__global__ __launch_bounds__(256) void k_dec_sync(SyncArgs a) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= a.nchunks) return;
-  const DecJob &job = a.jobs[job_of(a.jobs, a.njobs, c)];
-  const int lc = c - job.chunk0;
-  long long entry;
-  if (a.first || lc == 0) {
-    entry = pack_state((long long)lc * CHUNK, 0);
-    if (!a.first) {
-      a.exit_out[c] = a.exit_in[c];
-      return;
-    }
-  } else {
-    entry = a.exit_in[c - 1];
-    if (entry < 0) entry = pack_state((long long)lc * CHUNK, 0);  // predecessor met a bad code
-    if (entry == a.entry_pos[c]) {
-      a.exit_out[c] = a.exit_in[c];
-      return;
-    }
-    *a.changed = 1;
-  }
-  a.entry_pos[c] = entry;
-  Bits br{(const unsigned long long *)(a.blob + job.data)};
-  long long pos = entry >> 6;
-  int k = (int)(entry & 63);
-  const long long stop = min((long long)(lc + 1) * CHUNK, job.nbits);
-  bool bad;
-  const int n = decode_span<false>(br, pos, k, stop, a.tabs[job.dc], a.tabs[job.ac], nullptr, 0,
-                                   (long long)job.nblocks, &bad);
-  a.nblk[c] = n;
-  a.exit_out[c] = bad ? -1 : pack_state(pos, k);
-}
-
-// per scan: exclusive scan of the chunks' block counts (one workgroup per
-// scan, sequential over 256-chunk tiles) and the total check
-__global__ __launch_bounds__(256) void k_dec_scan(const DecJob *jobs, const int *nblk, long long *base,
-                                                  int *status) {
-  __shared__ long long part[256];
-  const DecJob job = jobs[blockIdx.x];
-  long long carry = 0;
-  for (int t0 = 0; t0 < job.nchunks; t0 += 256) {
-    const int t = t0 + threadIdx.x;
-    const long long v = t < job.nchunks ? nblk[job.chunk0 + t] : 0;
-    part[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-      const long long add = threadIdx.x >= o ? part[threadIdx.x - o] : 0;
-      __syncthreads();
-      part[threadIdx.x] += add;
-      __syncthreads();
-    }
-    if (t < job.nchunks) base[job.chunk0 + t] = carry + part[threadIdx.x] - v;
-    const long long tot = part[255];
-    __syncthreads();
-    carry += tot;
-  }
-  // a chunk that decodes the last block may go on through the pad bits
-  // (and count garbage blocks there); fewer blocks than the frame needs is
-  // a truncated stream
-  if (threadIdx.x == 0) status[blockIdx.x] = carry >= job.nblocks ? 0 : 5;
-}
-
-// final pass: every chunk decodes from its settled entry and writes.  A
-// lane assembles each block in its own LDS slot (128 B) and stores it whole
-// (8 x 16 B, zeros included: no memset of the planes).  A block split
-// between two chunks is stored in halves with 2-byte stores: the lane that
-// started it writes positions [first, k_exit), the next lane [k_entry, 64)
-// -- the settled states make k_exit == k_entry.
-__global__ __launch_bounds__(256) void k_dec_write(SyncArgs a, const long long *base, int16_t *coefs,
-                                                   int *status) {
-  __shared__ int4 slot[256][8];
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= a.nchunks) return;
-  const int j = job_of(a.jobs, a.njobs, c);
-  const DecJob &job = a.jobs[j];
-  const int lc = c - job.chunk0;
-  const long long entry = a.entry_pos[c];
-  long long pos = entry >> 6;
-  int k = (int)(entry & 63);
-  // the block in progress at the entry was started by an earlier chunk
-  long long blk = base[c] - (k ? 1 : 0);
-  if (blk >= job.nblocks) return;  // pad bits after the last block
-  Bits br{(const unsigned long long *)(a.blob + job.data)};
-  const long long stop = min((long long)(lc + 1) * CHUNK, job.nbits);
-  const DecTab &dc = a.tabs[job.dc], &ac = a.tabs[job.ac];
-  int4 *sl = slot[threadIdx.x];
-  int16_t *b16 = (int16_t *)sl;
-  int16_t *out = coefs + job.out;
-#pragma unroll
-  for (int q = 0; q < 8; q++) sl[q] = int4{0, 0, 0, 0};
-  int first = k;
-  bool bad = false;
-  while (pos < stop && blk < job.nblocks) {
-    int sym, val;
-    const int n = decode_one(br, pos, k ? ac : dc, sym, val);
-    if (!n) {
-      bad = true;
-      break;
-    }
-    pos += n;
-    if (k == 0) {
-      if (sym > 15) {
-        bad = true;
-        break;
-      }
-      b16[0] = (int16_t)val;
-      k = 1;
-    } else {
-      const int r = sym >> 4;
-      if (sym & 15) {
-        k += r;
-        if (k > 63) {
-          bad = true;
-          break;
-        }
-        b16[k++] = (int16_t)val;
-      } else {
-        k = r == 15 ? k + 16 : 64;  // ZRL / EOB
-      }
-    }
-    if (k >= 64) {  // block complete: store it, clear the slot
-      int16_t *o = out + 64 * blk;
-      if (first == 0) {
-#pragma unroll
-        for (int q = 0; q < 8; q++) ((int4 *)o)[q] = sl[q];
-      } else {
-        for (int t = first; t < 64; t++) o[t] = b16[t];
-      }
-#pragma unroll
-      for (int q = 0; q < 8; q++) sl[q] = int4{0, 0, 0, 0};
-      first = 0;
-      k = 0;
-      blk++;
-    }
-  }
-  if (!bad && k && blk < job.nblocks) {  // block continues in the next chunk
-    int16_t *o = out + 64 * blk;
-    for (int t = first; t < k; t++) o[t] = b16[t];
-  }
-  if (bad) atomicMax(&status[j], 6);
-}
-
-// ---------------------------------------------------------------------------
-// Pixels (DESIGN.md "Decode to pixels"): libjpeg's "islow" IDCT, h2v2 "fancy"
-// upsampling and fixed-point colour conversion, integer only, in two passes
-// through uint8 planes: k_dec_dc + k_dec_dcbase (absolute DCs), k_dec_idct
-// (coefficients -> Y / Cb / Cr samples), k_dec_colour (samples -> packed
-// 3-byte pixels).  The arithmetic itself is mij_pixels.h.
-// The IDCT's sums run in uint32_t: streams no 8-bit image produces wrap
-// instead of overflowing a signed type; encoder-made streams never wrap.
-// ---------------------------------------------------------------------------
-struct RecJob {     // one component of one frame
-  long long off;    // first int16 of its coefficient plane == first byte of its sample plane
-  int nblocks, bw;  // 8x8 blocks, and blocks per row
-  int wg0;          // its first workgroup in k_dec_idct's grid
-  int qt;           // its quantiser: 64 ints (zigzag order) at q + 64 * qt
-  int tile0;        // its first workgroup in k_dec_dc's grid == its first entry of the tile bases
-  int pad;
-};
-
-struct RecFrame {
-  long long planes;  // first byte of the Y plane; Cb at + w*h, Cr at + w*h*5/4
-  long long pix;     // first byte of the pixels, rows 3*w bytes apart
-  int w, h;
-  int wg0;           // its first workgroup in k_dec_colour's grid
-  int pad;
-};
-
-// Absolute DCs in two levels.  A plane's blocks are cut into tiles of
-// DC_TILE; k_dec_dc, one 1024-lane workgroup per tile (so luma and chroma
-// planes load the chip alike), writes every block's DC relative to its tile
-// (each lane DC_PER consecutive blocks, a shuffle scan per wave, the waves'
-// totals through LDS) to dc[off / 64 + block] and the tile's total to
-// tile[blockIdx.x]; k_dec_dcbase, one lane per plane, turns the totals into
-// each tile's base.  k_dec_idct adds the two.  All sums modulo 2^32.
-constexpr int DC_T = 1024, DC_PER = 8, DC_TILE = DC_T * DC_PER;
-
-template <class J>
-__device__ __forceinline__ int rec_tile_job(const J *jobs, int njobs, int tile) {
-  int lo = 0, hi = njobs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (jobs[mid].tile0 <= tile) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-__global__ __launch_bounds__(DC_T) void k_dec_dc(const RecJob *jobs, int njobs, const int16_t *coefs, int32_t *dc,
-                                                 uint32_t *tile) {
-  __shared__ uint32_t wsum[DC_T / 64];
-  const RecJob job = jobs[rec_tile_job(jobs, njobs, blockIdx.x)];
-  const int16_t *src = coefs + job.off;
-  int32_t *dst = dc + job.off / 64;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int b0 = ((int)blockIdx.x - job.tile0) * DC_TILE + (int)threadIdx.x * DC_PER;
-  uint32_t v[DC_PER], s = 0;
-#pragma unroll
-  for (int i = 0; i < DC_PER; i++) {
-    if (b0 + i < job.nblocks) s += (uint32_t)(int32_t)src[64LL * (b0 + i)];
-    v[i] = s;
-  }
-  uint32_t x = s;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wsum[wave] = x;
-  __syncthreads();
-  uint32_t base = x - s, tot = 0;
-#pragma unroll
-  for (int k = 0; k < DC_T / 64; k++) {
-    const uint32_t t = wsum[k];
-    if (k < wave) base += t;
-    tot += t;
-  }
-#pragma unroll
-  for (int i = 0; i < DC_PER; i++)
-    if (b0 + i < job.nblocks) dst[b0 + i] = (int32_t)(base + v[i]);
-  if (threadIdx.x == 0) tile[blockIdx.x] = tot;
-}
-
-// tile totals -> exclusive prefix within each plane (a 3840x2160 luma plane
-// has 16 tiles)
-template <class J>
-__global__ __launch_bounds__(64) void k_dec_dcbase(const J *jobs, int njobs, uint32_t *tile) {
-  const int j = blockIdx.x * 64 + threadIdx.x;
-  if (j >= njobs) return;
-  const int t0 = jobs[j].tile0, nt = (jobs[j].nblocks + DC_TILE - 1) / DC_TILE;
-  uint32_t run = 0;
-  for (int t = 0; t < nt; t++) {
-    const uint32_t v = tile[t0 + t];
-    tile[t0 + t] = run;
-    run += v;
-  }
-}
-
-template <class J>
-__device__ __forceinline__ int rec_job_of(const J *jobs, int njobs, int wg) {
-  int lo = 0, hi = njobs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (jobs[mid].wg0 <= wg) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-// One lane per 8x8 block, 256 blocks of one component per workgroup.  The
-// workgroup's 32 KiB of coefficients come in with coalesced 16-byte loads
-// and are staged in LDS, a block's 8 int4 in a slot of 9 (a lane's 16-byte
-// reads then fall on distinct bank groups); the lane dequantises into
-// natural order (all indices compile-time: registers), runs the column pass
-// (descale 11) and the row pass (descale 18), and stores 8 bytes per row.
-__global__ __launch_bounds__(256) void k_dec_idct(const RecJob *jobs, int njobs, const int16_t *coefs,
-                                                  const int32_t *dc, const uint32_t *tile, const int32_t *q,
-                                                  uint8_t *planes) {
-  __shared__ int4 stage[256 * 9];
-  const RecJob job = jobs[rec_job_of(jobs, njobs, blockIdx.x)];
-  const int first = ((int)blockIdx.x - job.wg0) * 256;
-  const int nb = min(256, job.nblocks - first);
-  const int4 *src = (const int4 *)(coefs + job.off + 64LL * first);
-  for (int i = threadIdx.x; i < nb * 8; i += 256) stage[(i >> 3) * 9 + (i & 7)] = src[i];
-  __syncthreads();
-  if ((int)threadIdx.x >= nb) return;
-  const int blk = first + threadIdx.x;
-  union {
-    int4 v[8];
-    int16_t c[64];
-  } in;
-#pragma unroll
-  for (int k = 0; k < 8; k++) in.v[k] = stage[threadIdx.x * 9 + k];
-  uint32_t rows[8][2];
-  const uint32_t dc_abs = (uint32_t)dc[job.off / 64 + blk] + tile[job.tile0 + blk / DC_TILE];
-  idct_block(in.c, dc_abs, q + 64 * job.qt, rows);
-  const int by = blk / job.bw, bx = blk - by * job.bw;
-  const long long pitch = 8LL * job.bw;
-  uint8_t *dst = planes + job.off + 8LL * by * pitch + 8 * bx;
-#pragma unroll
-  for (int r = 0; r < 8; r++)  // 8-byte aligned: off % 64 == 0, pitch % 8 == 0
-    store_as(dst + r * pitch, W2{rows[r][0], rows[r][1]});
-}
-
-template <class F>
-__device__ __forceinline__ int rec_frame_of(const F *fr, int n, int wg) {
+// the last entry of a table sorted by KEY whose KEY is <= v (entry 0 if none is)
+template <auto KEY, class T>
+__device__ __forceinline__ int last_le(const T *tab, int n, int v) {
   int lo = 0, hi = n - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
-    if (fr[mid].wg0 <= wg) lo = mid;
+    if (tab[mid].*KEY <= v) lo = mid;
     else hi = mid - 1;
   }
   return lo;
 }
 
-// One lane per 16 x 2 output pixels (colour_tile, mij_pixels.h), a frame's
-// tiles in raster order, 256 per workgroup; no workgroup spans two frames.
-__global__ __launch_bounds__(256) void k_dec_colour(const RecFrame *frames, int nframes, const uint8_t *planes,
-                                                    uint8_t *pix, int rgb) {
-  const RecFrame fr = frames[rec_frame_of(frames, nframes, blockIdx.x)];
-  const int groups = fr.w >> 4;
-  const int idx = ((int)blockIdx.x - fr.wg0) * 256 + (int)threadIdx.x;
-  if (idx >= (fr.h >> 1) * groups) return;
-  const int r = idx / groups, g = idx - r * groups;
-  const uint8_t *Y = planes + fr.planes;
-  const uint8_t *Cb = Y + (long long)fr.w * fr.h, *Cr = Cb + ((long long)fr.w * fr.h >> 2);
-  colour_tile(Y, Cb, Cr, fr.w, fr.h, r, g, rgb, pix + fr.pix);
-}
-
 // ---------------------------------------------------------------------------
-// Interleaved scans (DESIGN.md "Decoding ordinary baseline files"): one scan
-// holds MCUs of up to 6 blocks, cut into restart intervals.  An interval is
-// what a scan is above: its own zero-padded slot of the blob, its own chunks,
-// an exact entry (first bit, k 0, slot 0) for its first chunk.  A chunk's
-// state is (bit position, coefficient index k, block slot within the MCU);
-// the Huffman tables follow the slot.
+// Entropy decoding (DESIGN.md "Decoding ordinary baseline files").  A scan
+// holds MCUs of up to 6 blocks, cut into restart intervals; a one-component
+// scan (the encoder's streams hold three) is a scan whose MCU is one block:
+// bpm == 1, hs == vs == 1, mcus_x == bw, never reset.  An interval has its
+// own zero-padded slot of the blob, its own chunks and an exact entry (first
+// bit, k 0, slot 0) for its first chunk.  A chunk's state is (bit position,
+// coefficient index k, block slot within the MCU); the Huffman tables follow
+// the slot.
 //
 // Bounds, whatever the bits say.  Reads: a window is taken only at pos <
 // stop <= nbits and covers words pos/64 and pos/64 + 1, i.e. at most 15
 // bytes past the interval's last byte; every slot ends in >= 16 zero bytes.
 // States: k leaves a span in 0..63 (a run past 63 is "bad", ZRL / EOB end
 // the block), slot in 0..bpm-1 (only ever stepped modulo bpm), and a state
-// is only ever produced by these kernels.  Stores: k_il_write stores block
+// is only ever produced by these kernels.  Stores: k_dec_write stores block
 // b of interval i only while b < nmcus_i * bpm, to MCU mcu0_i + b / bpm <
-// the frame's MCU count (the host checks mcu0_i + nmcus_i <= mcus_x *
+// the scan's MCU count (the host checks mcu0_i + nmcus_i <= mcus_x *
 // mcus_y before any launch), at a position inside that MCU (slot_x < h_c,
 // slot_y < v_c), hence inside the component's padded plane; b itself comes
 // from the prefix sum and is checked >= 0 and congruent to the entry slot
-// first.  A stream that breaks any of this ends in a status code.
+// first.  A one-component scan is the case bpm == 1: the slot is always 0,
+// block b < nmcus is MCU b, and it is stored at raster block b of a plane of
+// bw * bh == nmcus blocks.  A stream that breaks any of this ends in a
+// status code.
 // ---------------------------------------------------------------------------
-struct IlFrame {
-  long long off[3];  // first int16 of each component's padded plane
-  int ncomp, bpm;    // blocks per MCU
+struct DecScan {
+  long long off[3];  // first int16 of each of its components' padded planes
+  int ncomp, bpm;    // blocks per MCU; bpm == 1 implies hs == vs == 1 and bw == mcus_x
   int mcus_x, nmcus;
-  int chunk0, nchunks;  // all chunks of the frame's intervals, contiguous
+  int chunk0, nchunks;  // all chunks of the scan's intervals, contiguous
   int hs[3], vs[3], bw[3];
   int dc[3], ac[3];  // table indices per component
   int slot_comp[6], slot_x[6], slot_y[6];
 };
 
-struct IlJob {          // one restart interval (a whole scan without DRI)
-  long long data, nbits;  // as DecJob
-  int frame;            // index into the IlFrame table
+struct DecIvl {         // one restart interval (a whole scan without DRI)
+  long long data;       // byte offset of the UNSTUFFED interval in the blob (8-aligned)
+  long long nbits;      // its length in bits (the pad bits included)
+  int scan;             // index into the DecScan table
   int mcu0, nmcus;
-  int chunk0, nchunks;
+  int chunk0, nchunks;  // global ids of the interval's chunks
   int pad;
 };
 
-struct IlArgs {
+struct DecArgs {
   const uint8_t *blob;
-  const IlJob *jobs;
-  const IlFrame *frames;
-  int njobs, nchunks;
+  const DecIvl *jobs;
+  const DecScan *scans;
+  int njobs;
+  int chunk0, chunk1;  // the chunks this launch covers
   const DecTab *tabs;
   long long *entry_pos, *exit_in, *exit_out;  // (pos * 8 + slot) * 64 + k
   int *nblk;
@@ -574,36 +192,38 @@ struct IlArgs {
   int first;
 };
 
-__device__ __forceinline__ long long il_pack(long long pos, int slot, int k) { return (pos * 8 + slot) * 64 + k; }
+__device__ __forceinline__ long long pack_state(long long pos, int slot, int k) { return (pos * 8 + slot) * 64 + k; }
 
-__device__ __forceinline__ int il_job_of(const IlJob *jobs, int njobs, int c) {
-  int lo = 0, hi = njobs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (jobs[mid].chunk0 <= c) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-// k_dec_sync for intervals: the same passes, the state one field wider.  A
-// chunk decodes again only when its predecessor's exit state, slot included,
-// changed.
-__global__ __launch_bounds__(256) void k_il_sync(IlArgs a) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= a.nchunks) return;
-  const IlJob &job = a.jobs[il_job_of(a.jobs, a.njobs, c)];
+// Self-synchronising pass (Weissenberger & Schmidt, ICPP 2018): chunk c
+// decodes from its entry state to its end.  First pass: every chunk starts
+// at its first bit as if an MCU began there (exact for chunk 0 of an
+// interval).  Later passes: the entry of chunk c is the exit of chunk c-1
+// from the previous pass; a chunk whose entry, slot included, did not change
+// keeps its result.  Huffman streams resynchronise within a few symbols, so
+// 2-3 passes settle.
+//
+// ONE (this kernel and k_dec_write): every chunk of the launch belongs to a
+// scan of one-block MCUs.  The host puts those scans' chunks first and
+// launches them apart, so that slot 0, bpm 1 and the scan's one pair of
+// tables are compile-time facts there: the same source measured 6 % (this
+// kernel) and 10 % (k_dec_write) slower on the encoder's streams with them
+// read per block.
+template <bool ONE>
+__global__ __launch_bounds__(256) void k_dec_sync(DecArgs a) {
+  const int c = a.chunk0 + blockIdx.x * 256 + threadIdx.x;
+  if (c >= a.chunk1) return;
+  const DecIvl &job = a.jobs[last_le<&DecIvl::chunk0>(a.jobs, a.njobs, c)];
   const int lc = c - job.chunk0;
   long long entry;
   if (a.first || lc == 0) {
-    entry = il_pack((long long)lc * CHUNK, 0, 0);
+    entry = pack_state((long long)lc * CHUNK, 0, 0);
     if (!a.first) {
       a.exit_out[c] = a.exit_in[c];
       return;
     }
   } else {
     entry = a.exit_in[c - 1];
-    if (entry < 0) entry = il_pack((long long)lc * CHUNK, 0, 0);  // predecessor met a bad code
+    if (entry < 0) entry = pack_state((long long)lc * CHUNK, 0, 0);  // predecessor met a bad code
     if (entry == a.entry_pos[c]) {
       a.exit_out[c] = a.exit_in[c];
       return;
@@ -611,14 +231,15 @@ __global__ __launch_bounds__(256) void k_il_sync(IlArgs a) {
     *a.changed = 1;
   }
   a.entry_pos[c] = entry;
-  const IlFrame &F = a.frames[job.frame];
+  const DecScan &S = a.scans[job.scan];
+  const int bpm = ONE ? 1 : S.bpm;
   Bits br{(const unsigned long long *)(a.blob + job.data)};
   long long pos = entry >> 9;
-  int slot = (int)(entry >> 6) & 7, k = (int)(entry & 63);
+  int slot = ONE ? 0 : (int)(entry >> 6) & 7, k = (int)(entry & 63);
   const long long stop = min((long long)(lc + 1) * CHUNK, job.nbits);
-  long long blocks_left = (long long)job.nmcus * F.bpm;
-  int comp = F.slot_comp[slot];
-  const DecTab *dc = a.tabs + F.dc[comp], *ac = a.tabs + F.ac[comp];
+  long long blocks_left = (long long)job.nmcus * bpm;
+  int comp = ONE ? 0 : S.slot_comp[slot];
+  const DecTab *dc = a.tabs + S.dc[comp], *ac = a.tabs + S.ac[comp];
   int started = 0;
   bool bad = false;
   while (pos < stop) {
@@ -655,22 +276,25 @@ __global__ __launch_bounds__(256) void k_il_sync(IlArgs a) {
     if (k >= 64) {
       k = 0;
       blocks_left--;
-      slot = slot + 1 == F.bpm ? 0 : slot + 1;
-      comp = F.slot_comp[slot];
-      dc = a.tabs + F.dc[comp];
-      ac = a.tabs + F.ac[comp];
+      if (!ONE) {
+        slot = slot + 1 == bpm ? 0 : slot + 1;
+        comp = S.slot_comp[slot];
+        dc = a.tabs + S.dc[comp];
+        ac = a.tabs + S.ac[comp];
+      }
     }
   }
   a.nblk[c] = started;
-  a.exit_out[c] = bad ? -1 : il_pack(pos, slot, k);
+  a.exit_out[c] = bad ? -1 : pack_state(pos, slot, k);
 }
 
-// per frame (not per interval: a file may hold thousands of one-MCU
-// intervals): exclusive scan of its chunks' block counts across all its
-// intervals.  k_il_write takes differences against its interval's first chunk.
-__global__ __launch_bounds__(256) void k_il_scan(const IlFrame *frames, const int *nblk, long long *base) {
+// per scan (not per interval: a file may hold thousands of one-MCU
+// intervals; one workgroup each, sequential over 256-chunk tiles): exclusive
+// scan of its chunks' block counts across all its intervals.  k_dec_write
+// takes differences against its interval's first chunk.
+__global__ __launch_bounds__(256) void k_dec_scan(const DecScan *scans, const int *nblk, long long *base) {
   __shared__ long long part[256];
-  const int chunk0 = frames[blockIdx.x].chunk0, nchunks = frames[blockIdx.x].nchunks;
+  const int chunk0 = scans[blockIdx.x].chunk0, nchunks = scans[blockIdx.x].nchunks;
   long long carry = 0;
   for (int t0 = 0; t0 < nchunks; t0 += 256) {
     const int t = t0 + threadIdx.x;
@@ -690,32 +314,52 @@ __global__ __launch_bounds__(256) void k_il_scan(const IlFrame *frames, const in
   }
 }
 
-// k_dec_write for intervals.  Scan-order block b of the interval lies in MCU
-// mcu0 + b / bpm at slot b % bpm; its place is that component's padded plane,
-// block row my * v_c + slot_y, block column mx * h_c + slot_x.  status: one
-// int per frame; 5 = an interval holds fewer blocks than its MCUs need, 6 =
+// Scan-order block `slot` of MCU `mcu` lies in that component's padded plane
+// at block row my * v_c + slot_y, block column mx * h_c + slot_x; for a
+// one-block MCU (h_c == v_c == 1, bw == mcus_x) that is raster block `mcu`.
+template <bool ONE>
+__device__ __forceinline__ int16_t *scan_block(const DecScan &S, int16_t *coefs, int mcu, int slot, int comp) {
+  if (ONE) return coefs + S.off[0] + 64LL * mcu;
+  const int my = mcu / S.mcus_x, mx = mcu - my * S.mcus_x;
+  return coefs + S.off[comp] +
+         64 * ((long long)(my * S.vs[comp] + S.slot_y[slot]) * S.bw[comp] + mx * S.hs[comp] + S.slot_x[slot]);
+}
+
+// final pass: every chunk decodes from its settled entry and writes.  A
+// lane assembles each block in its own LDS slot (128 B) and stores it whole
+// (8 x 16 B, zeros included: no memset of the planes).  A block split
+// between two chunks is stored in halves with 2-byte stores: the lane that
+// started it writes positions [first, k_exit), the next lane [k_entry, 64)
+// -- the settled states make k_exit == k_entry.  Scan-order block b of the
+// interval lies in MCU mcu0 + b / bpm at slot b % bpm (scan_block).  A
+// chunk that decodes the last block may go on through the pad bits; fewer
+// blocks than the interval's MCUs need is a truncated stream.  status: one
+// int per scan; 5 = an interval holds fewer blocks than its MCUs need, 6 =
 // invalid code, 7 = the prefix sum and the settled slot disagree.
-__global__ __launch_bounds__(256) void k_il_write(IlArgs a, const long long *base, int16_t *coefs, int *status) {
+template <bool ONE>
+__global__ __launch_bounds__(256) void k_dec_write(DecArgs a, const long long *base, int16_t *coefs, int *status) {
   __shared__ int4 slotbuf[256][8];
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= a.nchunks) return;
-  const IlJob &job = a.jobs[il_job_of(a.jobs, a.njobs, c)];
-  const IlFrame &F = a.frames[job.frame];
+  const int c = a.chunk0 + blockIdx.x * 256 + threadIdx.x;
+  if (c >= a.chunk1) return;
+  const DecIvl &job = a.jobs[last_le<&DecIvl::chunk0>(a.jobs, a.njobs, c)];
+  const DecScan &S = a.scans[job.scan];
+  const int bpm = ONE ? 1 : S.bpm;
+  const DecTab &dc1 = a.tabs[S.dc[0]], &ac1 = a.tabs[S.ac[0]];  // ONE: the scan's only tables
   const int lc = c - job.chunk0;
-  const long long nblocks = (long long)job.nmcus * F.bpm;
+  const long long nblocks = (long long)job.nmcus * bpm;
   const long long lb = base[c] - base[job.chunk0];  // blocks the interval's earlier chunks started
-  if (lc == job.nchunks - 1 && lb + a.nblk[c] < nblocks) atomicMax(&status[job.frame], 5);
+  if (lc == job.nchunks - 1 && lb + a.nblk[c] < nblocks) atomicMax(&status[job.scan], 5);
   const long long entry = a.entry_pos[c];
   long long pos = entry >> 9;
-  int slot = (int)(entry >> 6) & 7, k = (int)(entry & 63);
+  int slot = ONE ? 0 : (int)(entry >> 6) & 7, k = (int)(entry & 63);
   // the block in progress at the entry was started by an earlier chunk
   long long blk = lb - (k ? 1 : 0);
   if (blk >= nblocks) return;  // pad bits after the last block
-  if (blk < 0 || (int)(blk % F.bpm) != slot) {
-    atomicMax(&status[job.frame], 7);
+  if (blk < 0 || (int)(blk % bpm) != slot) {
+    atomicMax(&status[job.scan], 7);
     return;
   }
-  int mcu = job.mcu0 + (int)(blk / F.bpm);
+  int mcu = job.mcu0 + (int)(blk / bpm);
   Bits br{(const unsigned long long *)(a.blob + job.data)};
   const long long stop = min((long long)(lc + 1) * CHUNK, job.nbits);
   int4 *sl = slotbuf[threadIdx.x];
@@ -725,9 +369,9 @@ __global__ __launch_bounds__(256) void k_il_write(IlArgs a, const long long *bas
   int first = k;
   bool bad = false;
   while (pos < stop && blk < nblocks) {
-    const int comp = F.slot_comp[slot];
+    const int comp = ONE ? 0 : S.slot_comp[slot];
     int sym, val;
-    const int n = decode_one(br, pos, a.tabs[k ? F.ac[comp] : F.dc[comp]], sym, val);
+    const int n = decode_one(br, pos, ONE ? (k ? ac1 : dc1) : a.tabs[k ? S.ac[comp] : S.dc[comp]], sym, val);
     if (!n) {
       bad = true;
       break;
@@ -754,9 +398,7 @@ __global__ __launch_bounds__(256) void k_il_write(IlArgs a, const long long *bas
       }
     }
     if (k >= 64) {  // block complete: store it, clear the slot
-      const int my = mcu / F.mcus_x, mx = mcu - my * F.mcus_x;
-      int16_t *o = coefs + F.off[comp] +
-                   64 * ((long long)(my * F.vs[comp] + F.slot_y[slot]) * F.bw[comp] + mx * F.hs[comp] + F.slot_x[slot]);
+      int16_t *o = scan_block<ONE>(S, coefs, mcu, slot, comp);
       if (first == 0) {
 #pragma unroll
         for (int q = 0; q < 8; q++) ((int4 *)o)[q] = sl[q];
@@ -768,55 +410,66 @@ __global__ __launch_bounds__(256) void k_il_write(IlArgs a, const long long *bas
       first = 0;
       k = 0;
       blk++;
-      if (++slot == F.bpm) {
+      if (++slot == bpm) {
         slot = 0;
         mcu++;
       }
     }
   }
   if (!bad && k && blk < nblocks) {  // block continues in the next chunk
-    const int comp = F.slot_comp[slot];
-    const int my = mcu / F.mcus_x, mx = mcu - my * F.mcus_x;
-    int16_t *o = coefs + F.off[comp] +
-                 64 * ((long long)(my * F.vs[comp] + F.slot_y[slot]) * F.bw[comp] + mx * F.hs[comp] + F.slot_x[slot]);
+    int16_t *o = scan_block<ONE>(S, coefs, mcu, slot, ONE ? 0 : S.slot_comp[slot]);
     for (int t = first; t < k; t++) o[t] = b16[t];
   }
-  if (bad) atomicMax(&status[job.frame], 6);
+  if (bad) atomicMax(&status[job.scan], 6);
 }
 
-// Reconstruction for these frames.  DC prediction runs per component in scan
-// order (inside an MCU left-right, top-bottom, then the next MCU) and starts
-// again at 0 every restart interval, i.e. every `seg` blocks of the
-// component.  k_il_dc is k_dec_dc over scan-order index s instead of raster
-// order: dc[off / 64 + s] = the sum of differences 0..s relative to the tile,
-// tile totals as before, k_dec_dcbase unchanged.  With P(s) = dc + tile base,
-// block s has absolute DC P(s) - P(first block of its segment - 1): two loads
-// in k_il_idct, no segmented scan.  All modulo 2^32.
-struct IlRec {      // one component of one frame
-  long long off;    // as RecJob
-  int nblocks, bw;  // padded plane: blocks, and blocks per row (mcus_x * h_c)
-  int wg0, qt, tile0;
-  int hs, vs, mcus_x;
-  int seg;          // blocks between DC resets: Ri * h_c * v_c, nblocks without DRI
-  int pad;
+// ---------------------------------------------------------------------------
+// Pixels (DESIGN.md "Decode to pixels", §4j for the reduced sizes): libjpeg's
+// "islow" IDCT and its reduced IDCTs, "fancy" upsampling and fixed-point
+// colour conversion, integer only, in two passes through uint8 planes:
+// k_dec_dc + k_dec_dcbase (absolute DCs), k_dec_idct<S> (coefficients -> Y /
+// Cb / Cr samples, S x S per block), k_dec_colour (samples -> packed 3-byte
+// pixels).  The arithmetic itself is mij_pixels.h.
+// The IDCT's sums run in uint32_t: streams no 8-bit image produces wrap
+// instead of overflowing a signed type; encoder-made streams never wrap.
+// ---------------------------------------------------------------------------
+struct RecJob {      // one component of one frame
+  long long off;     // first int16 of its coefficient plane == first byte of its sample plane
+  int nblocks, bw, bh;  // padded plane: 8x8 blocks, blocks per row (mcus_x * h_c), block rows
+  int wg0;           // its first workgroup in k_dec_idct's grid
+  int qt;            // its quantiser: 64 ints (zigzag order) at q + 64 * qt
+  int tile0;         // its first workgroup in k_dec_dc's grid == its first entry of the tile bases
+  int hs, vs, mcus_x;  // its scan's order: blocks per MCU across and down, MCUs across
+  int seg;           // blocks between DC resets: Ri * h_c * v_c, nblocks without DRI
+  int pitch;         // bytes between the sample plane's rows
+  int spr;           // strips of 8 samples per block row: ceil(bw * S / 8)
 };
 
-// scan-order index -> raster index in the padded plane, and back
-__device__ __forceinline__ int il_raster(const IlRec &j, int s) {
+// Absolute DCs in two levels.  DC prediction runs per component in scan order
+// (inside an MCU left-right, top-bottom, then the next MCU; raster order for a
+// one-component scan) and starts again at 0 every restart interval, i.e.
+// every `seg` blocks of the component.  A component's blocks are cut, in scan
+// order, into tiles of DC_TILE; k_dec_dc, one 1024-lane workgroup per tile (so
+// luma and chroma planes load the chip alike), writes the sum of differences
+// 0..s relative to the tile (each lane DC_PER consecutive blocks, a shuffle
+// scan per wave, the waves' totals through LDS) to dc[off / 64 + s] and the
+// tile's total to tile[blockIdx.x]; k_dec_dcbase, one lane per plane, turns
+// the totals into each tile's base.  With P(s) = dc + tile base, block s has
+// absolute DC P(s) - P(first block of its segment - 1): two loads in
+// k_dec_idct, no segmented scan.  All sums modulo 2^32.
+constexpr int DC_T = 1024, DC_PER = 8, DC_TILE = DC_T * DC_PER;
+
+// scan-order index -> raster index in the padded plane
+__device__ __forceinline__ int scan_to_raster(const RecJob &j, int s) {
   const int hv = j.hs * j.vs, m = s / hv, i = s - m * hv;
   const int my = m / j.mcus_x, mx = m - my * j.mcus_x, iy = i / j.hs, ix = i - iy * j.hs;
   return (my * j.vs + iy) * j.bw + mx * j.hs + ix;
 }
-__device__ __forceinline__ int il_scan_index(const IlRec &j, int blk) {
-  const int by = blk / j.bw, bx = blk - by * j.bw;
-  const int my = by / j.vs, iy = by - my * j.vs, mx = bx / j.hs, ix = bx - mx * j.hs;
-  return (my * j.mcus_x + mx) * (j.hs * j.vs) + iy * j.hs + ix;
-}
 
-__global__ __launch_bounds__(DC_T) void k_il_dc(const IlRec *jobs, int njobs, const int16_t *coefs, int32_t *dc,
-                                                uint32_t *tile) {
+__global__ __launch_bounds__(DC_T) void k_dec_dc(const RecJob *jobs, int njobs, const int16_t *coefs, int32_t *dc,
+                                                 uint32_t *tile) {
   __shared__ uint32_t wsum[DC_T / 64];
-  const IlRec job = jobs[rec_tile_job(jobs, njobs, blockIdx.x)];
+  const RecJob job = jobs[last_le<&RecJob::tile0>(jobs, njobs, blockIdx.x)];
   const int16_t *src = coefs + job.off;
   int32_t *dst = dc + job.off / 64;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -824,7 +477,7 @@ __global__ __launch_bounds__(DC_T) void k_il_dc(const IlRec *jobs, int njobs, co
   uint32_t v[DC_PER], s = 0;
 #pragma unroll
   for (int i = 0; i < DC_PER; i++) {
-    if (b0 + i < job.nblocks) s += (uint32_t)(int32_t)src[64LL * il_raster(job, b0 + i)];
+    if (b0 + i < job.nblocks) s += (uint32_t)(int32_t)src[64LL * scan_to_raster(job, b0 + i)];
     v[i] = s;
   }
   uint32_t x = s;
@@ -848,61 +501,57 @@ __global__ __launch_bounds__(DC_T) void k_il_dc(const IlRec *jobs, int njobs, co
   if (threadIdx.x == 0) tile[blockIdx.x] = tot;
 }
 
-// k_dec_idct with the component's own quantiser and the DC rule above
-__global__ __launch_bounds__(256) void k_il_idct(const IlRec *jobs, int njobs, const int16_t *coefs, const int32_t *dc,
-                                                 const uint32_t *tile, const int32_t *q, uint8_t *planes) {
-  __shared__ int4 stage[256 * 9];
-  const IlRec job = jobs[rec_job_of(jobs, njobs, blockIdx.x)];
-  const int first = ((int)blockIdx.x - job.wg0) * 256;
-  const int nb = min(256, job.nblocks - first);
-  const int4 *src = (const int4 *)(coefs + job.off + 64LL * first);
-  for (int i = threadIdx.x; i < nb * 8; i += 256) stage[(i >> 3) * 9 + (i & 7)] = src[i];
-  __syncthreads();
-  if ((int)threadIdx.x >= nb) return;
-  const int blk = first + threadIdx.x;
-  union {
-    int4 v[8];
-    int16_t c[64];
-  } in;
-#pragma unroll
-  for (int k = 0; k < 8; k++) in.v[k] = stage[threadIdx.x * 9 + k];
-  const int s = il_scan_index(job, blk), s0 = s / job.seg * job.seg;
-  const int32_t *pd = dc + job.off / 64;
-  uint32_t dc_abs = (uint32_t)pd[s] + tile[job.tile0 + s / DC_TILE];
-  if (s0 > 0) dc_abs -= (uint32_t)pd[s0 - 1] + tile[job.tile0 + (s0 - 1) / DC_TILE];
-  uint32_t rows[8][2];
-  idct_block(in.c, dc_abs, q + 64 * job.qt, rows);
-  const int by = blk / job.bw, bx = blk - by * job.bw;
-  const long long pitch = 8LL * job.bw;
-  uint8_t *dst = planes + job.off + 8LL * by * pitch + 8 * bx;
-#pragma unroll
-  for (int r = 0; r < 8; r++) store_as(dst + r * pitch, W2{rows[r][0], rows[r][1]});
+// tile totals -> exclusive prefix within each plane (a 3840x2160 luma plane
+// has 16 tiles)
+__global__ __launch_bounds__(64) void k_dec_dcbase(const RecJob *jobs, int njobs, uint32_t *tile) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= njobs) return;
+  const int t0 = jobs[j].tile0, nt = (jobs[j].nblocks + DC_TILE - 1) / DC_TILE;
+  uint32_t run = 0;
+  for (int t = 0; t < nt; t++) {
+    const uint32_t v = tile[t0 + t];
+    tile[t0 + t] = run;
+    run += v;
+  }
 }
 
-struct IlPix {
-  long long y, cb, cr;  // first byte of each padded sample plane
-  long long pix;        // first byte of the pixels, rows G.pitch apart
-  PixGeom G;
-  int groups, units;    // 16-pixel groups per row; rows or row pairs (colour_tile_any)
-  int wg0, pad;
-};
-
-__global__ __launch_bounds__(256) void k_il_colour(const IlPix *frames, int nframes, const uint8_t *planes,
-                                                   uint8_t *pix, int rgb) {
-  const IlPix fr = frames[rec_frame_of(frames, nframes, blockIdx.x)];
-  const long long idx = ((long long)blockIdx.x - fr.wg0) * 256 + (int)threadIdx.x;
-  if (idx >= (long long)fr.units * fr.groups) return;
-  const int u = (int)(idx / fr.groups), g = (int)(idx - (long long)u * fr.groups);
-  colour_tile_any(planes + fr.y, planes + fr.cb, planes + fr.cr, fr.G, u, g, rgb, pix + fr.pix);
+// the absolute DC of raster block blk.  A 1x1 component's scan order is the
+// raster order (bw == mcus_x); without DC resets the segment begins at 0.
+// RASTER: the host found both true of every job of the launch (hs * vs == 1,
+// seg >= nblocks), so the rule is one prefix sum at blk < nblocks.
+template <bool RASTER>
+__device__ __forceinline__ uint32_t rec_dc(const RecJob &j, const int32_t *pd, const uint32_t *tile, int blk) {
+  if (RASTER) return (uint32_t)pd[blk] + tile[j.tile0 + blk / DC_TILE];
+  int s = blk;
+  if (j.hs * j.vs > 1) {
+    const int by = blk / j.bw, bx = blk - by * j.bw;
+    const int my = by / j.vs, iy = by - my * j.vs, mx = bx / j.hs, ix = bx - mx * j.hs;
+    s = (my * j.mcus_x + mx) * (j.hs * j.vs) + iy * j.hs + ix;
+  }
+  const int s0 = j.seg >= j.nblocks ? 0 : s / j.seg * j.seg;
+  uint32_t v = (uint32_t)pd[s] + tile[j.tile0 + s / DC_TILE];
+  if (s0 > 0) v -= (uint32_t)pd[s0 - 1] + tile[j.tile0 + (s0 - 1) / DC_TILE];
+  return v;
 }
 
-// ---------------------------------------------------------------------------
-// Decoding at 1/2, 1/4 and 1/8 scale.  The absolute DCs come
-// from the kernels above, unchanged; a component whose blocks become S x S
-// samples (mij_pixels.h scaled_geometry) goes through k_sc_idct<S> into a
-// plane whose rows are S * bw rounded up to 8 bytes apart, at the place its
-// full-size plane would take; k_il_colour then runs on the scaled geometry.
-// Frames of the encoder's own shape take the same path as any 4:2:0 frame.
+// A component whose blocks become S x S samples (8 at full size; at 1/2, 1/4
+// and 1/8 scale mij_pixels.h scaled_geometry says which) goes into a plane
+// whose rows are S * bw rounded up to 8 bytes apart, at the place its
+// full-size plane takes.
+//
+// One lane stores a strip: the 8 / S horizontally adjacent blocks of one
+// block row that make 8 output samples, so every row leaves as one aligned
+// 8-byte store.  A workgroup takes 256 * S / 8 consecutive strips, i.e. at
+// most 256 blocks, consecutive in raster order also where a block row ends
+// in a partial strip.  Its up to 32 KiB of coefficients come in with
+// coalesced 16-byte loads and are staged in LDS, a block's 8 int4 in a slot
+// of 9 (a lane's 16-byte reads then fall on distinct bank groups).  S == 8:
+// strip == block (spr == bw); the lane dequantises into natural order (all
+// indices compile-time: registers), runs the column pass (descale 11) and
+// the row pass (descale 18).  S == 4 and 2: every lane runs the IDCT of one
+// block (so none idles), leaves its S rows in LDS, in the staging area once
+// every lane has read its coefficients, and the strip lanes gather them.
+// S == 1 reads the DC buffers alone, 8 blocks per lane.
 //
 // Bounds.  A lane owns strip t < bh * spr of its component: block row by =
 // t / spr, blocks bx0 = (8 / S) * sx .. of which only those < bw are read.
@@ -912,52 +561,31 @@ __global__ __launch_bounds__(256) void k_il_colour(const IlPix *frames, int nfra
 // slot of the full-size plane.  In LDS a workgroup's block b < nb <= 256
 // has its staging slot at 9 * b int4 and its rows at words 256 * r + b,
 // r < S <= 4: both inside the 256 * 9 int4.  Nothing is addressed from data.
-// ---------------------------------------------------------------------------
-struct ScJob {      // one component of one frame
-  long long off;    // as RecJob
-  int nblocks, bw, bh;
-  int wg0, qt, tile0;
-  int hs, vs, mcus_x, seg;  // as IlRec (il only)
-  int il;           // the DC rule: 1 = k_il_idct's (scan order, segments), 0 = k_dec_idct's (raster)
-  int pitch;        // bytes between the scaled plane's rows
-  int spr;          // strips of 8 samples per block row: ceil(bw * S / 8)
-  int pad;
-};
-
-__device__ __forceinline__ uint32_t sc_dc(const ScJob &j, const int32_t *pd, const uint32_t *tile, int blk) {
-  if (!j.il) return (uint32_t)pd[blk] + tile[j.tile0 + blk / DC_TILE];
-  const int by = blk / j.bw, bx = blk - by * j.bw;
-  const int my = by / j.vs, iy = by - my * j.vs, mx = bx / j.hs, ix = bx - mx * j.hs;
-  const int s = (my * j.mcus_x + mx) * (j.hs * j.vs) + iy * j.hs + ix, s0 = s / j.seg * j.seg;
-  uint32_t v = (uint32_t)pd[s] + tile[j.tile0 + s / DC_TILE];
-  if (s0 > 0) v -= (uint32_t)pd[s0 - 1] + tile[j.tile0 + (s0 - 1) / DC_TILE];
-  return v;
-}
-
-// One lane stores a strip: the 8 / S horizontally adjacent blocks of one
-// block row that make 8 output samples, so every row leaves as one aligned
-// 8-byte store.  A workgroup takes 256 * S / 8 consecutive strips, i.e. at
-// most 256 blocks, consecutive in raster order also where a block row ends
-// in a partial strip; all 256 lanes stage their coefficients through LDS as
-// k_il_idct does.  For S == 4 and 2 every lane then runs the IDCT of one
-// block (so none idles), leaves its S rows in LDS, in the staging area once
-// every lane has read its coefficients, and the strip lanes gather them.
-// S == 8 is k_il_idct itself with the job's DC rule (4:2:0 chroma at 1/2);
-// S == 1 reads the DC buffers alone, 8 blocks per lane.
-template <int S>
-__global__ __launch_bounds__(256) void k_sc_idct(const ScJob *jobs, int njobs, const int16_t *coefs, const int32_t *dc,
-                                                 const uint32_t *tile, const int32_t *q, uint8_t *planes) {
+// A one-component scan's plane is the case hs == vs == 1, mcus_x == bw, seg
+// == nblocks: rec_dc reads entry blk < nblocks of its DC sums and no other.
+//
+// RASTER is launched at S == 8 only, over the planes that are coded in raster
+// order and never reset their DCs (every plane of the encoder's streams, the
+// 1x1 components of files without DRI).  With the rule decided per block at
+// run time this kernel took 0.58 .. 0.62 ms on 64 three-scan 3840x2160
+// frames, with it 0.54 .. 0.58.
+template <int S, bool RASTER>
+__global__ __launch_bounds__(256) void k_dec_idct(const RecJob *jobs, int njobs, const int16_t *coefs,
+                                                  const int32_t *dc, const uint32_t *tile, const int32_t *q,
+                                                  uint8_t *planes) {
   constexpr int PER = 8 / S, LANES = 256 / PER;
   __shared__ int4 stage[S > 1 ? 256 * 9 : 1];
-  const ScJob job = jobs[rec_job_of(jobs, njobs, blockIdx.x)];
-  const int nstrips = job.bh * job.spr;
+  const RecJob job = jobs[last_le<&RecJob::wg0>(jobs, njobs, blockIdx.x)];
+  const int spr = S == 8 ? job.bw : job.spr;  // S == 8: strip t is block t
+  const int nstrips = job.bh * spr;
   const int t0 = ((int)blockIdx.x - job.wg0) * LANES, t1 = min(t0 + LANES, nstrips);
-  const int by0 = t0 / job.spr, first = by0 * job.bw + (t0 - by0 * job.spr) * PER;
+  const int by0 = S == 8 ? 0 : t0 / spr, first = S == 8 ? t0 : by0 * job.bw + (t0 - by0 * spr) * PER;
   const int32_t *pd = dc + job.off / 64;
   const int32_t *qz = q + 64 * job.qt;
   int nb = 0;  // the workgroup's blocks: <= 256
   if (S > 1) {
-    const int by1 = t1 / job.spr, last = t1 == nstrips ? job.nblocks : by1 * job.bw + (t1 - by1 * job.spr) * PER;
+    const int by1 = S == 8 ? 0 : t1 / spr;
+    const int last = S == 8 ? t1 : t1 == nstrips ? job.nblocks : by1 * job.bw + (t1 - by1 * spr) * PER;
     nb = last - first;
     const int4 *src = (const int4 *)(coefs + job.off + 64LL * first);
     for (int i = threadIdx.x; i < nb * 8; i += 256) stage[(i >> 3) * 9 + (i & 7)] = src[i];
@@ -974,7 +602,7 @@ __global__ __launch_bounds__(256) void k_sc_idct(const ScJob *jobs, int njobs, c
       } in;
 #pragma unroll
       for (int j = 0; j < 8; j++) in.v[j] = stage[threadIdx.x * 9 + j];
-      const uint32_t dc_abs = sc_dc(job, pd, tile, first + (int)threadIdx.x);
+      const uint32_t dc_abs = rec_dc<RASTER>(job, pd, tile, first + (int)threadIdx.x);
       if constexpr (S == 4) idct4_block(in.c, dc_abs, qz, rows);
       else idct2_block(in.c, dc_abs, qz, rows);
     }
@@ -987,8 +615,8 @@ __global__ __launch_bounds__(256) void k_sc_idct(const ScJob *jobs, int njobs, c
   }
   const int t = t0 + (int)threadIdx.x;
   if ((int)threadIdx.x >= LANES || t >= t1) return;
-  const int by = t / job.spr, sx = t - by * job.spr;
-  const int blk0 = by * job.bw + sx * PER, nbl = min(PER, job.bw - sx * PER);
+  const int by = t / spr, sx = t - by * spr;
+  const int blk0 = S == 8 ? t : by * job.bw + sx * PER, nbl = S == 8 ? 1 : min(PER, job.bw - sx * PER);
   uint32_t out[S][2];
 #pragma unroll
   for (int r = 0; r < S; r++) out[r][0] = out[r][1] = 0;
@@ -997,7 +625,7 @@ __global__ __launch_bounds__(256) void k_sc_idct(const ScJob *jobs, int njobs, c
     if (k >= nbl) break;
     const int blk = blk0 + k;
     if constexpr (S == 1) {
-      out[0][k >> 2] |= idct1_block(sc_dc(job, pd, tile, blk), qz[0]) << (8 * (k & 3));
+      out[0][k >> 2] |= idct1_block(rec_dc<RASTER>(job, pd, tile, blk), qz[0]) << (8 * (k & 3));
     } else if constexpr (S == 8) {
       union {
         int4 v[8];
@@ -1005,7 +633,7 @@ __global__ __launch_bounds__(256) void k_sc_idct(const ScJob *jobs, int njobs, c
       } in;
 #pragma unroll
       for (int j = 0; j < 8; j++) in.v[j] = stage[(blk - first) * 9 + j];
-      idct_block(in.c, sc_dc(job, pd, tile, blk), qz, out);
+      idct_block(in.c, rec_dc<RASTER>(job, pd, tile, blk), qz, out);
     } else if constexpr (S == 4) {
 #pragma unroll
       for (int r = 0; r < 4; r++) out[r][k] = res[256 * r + blk - first];
@@ -1018,6 +646,27 @@ __global__ __launch_bounds__(256) void k_sc_idct(const ScJob *jobs, int njobs, c
 #pragma unroll
   for (int r = 0; r < S; r++)  // 8-byte aligned: off % 64 == 0, pitch % 8 == 0
     store_as(dst + (long long)r * job.pitch, W2{out[r][0], out[r][1]});
+}
+
+struct RecPix {         // one frame
+  long long y, cb, cr;  // first byte of each padded sample plane
+  long long pix;        // first byte of the pixels, rows G.pitch apart
+  PixGeom G;
+  int groups, units;    // 16-pixel groups per row; rows or row pairs (colour_tile_any)
+  int wg0, pad;         // its first workgroup in k_dec_colour's grid
+};
+
+// One lane per 16 x 1 or 16 x 2 output pixels (colour_tile_any, mij_pixels.h),
+// a frame's tiles in raster order, 256 per workgroup; no workgroup spans two
+// frames.
+__global__ __launch_bounds__(256) void k_dec_colour(const RecPix *frames, int nframes, const uint8_t *planes,
+                                                    uint8_t *pix, int rgb) {
+  const RecPix fr = frames[last_le<&RecPix::wg0>(frames, nframes, blockIdx.x)];
+  // (units * groups < 2^28: a frame is at most 65535 x 65535)
+  const int idx = ((int)blockIdx.x - fr.wg0) * 256 + (int)threadIdx.x;
+  if (idx >= fr.units * fr.groups) return;
+  const int u = idx / fr.groups, g = idx - u * fr.groups;
+  colour_tile_any(planes + fr.y, planes + fr.cb, planes + fr.cr, fr.G, u, g, rgb, pix + fr.pix);
 }
 
 }  // namespace mij
@@ -1290,17 +939,33 @@ int parse(const uint8_t *s, size_t n, Parsed &P, int frame) {
 
 // where a frame of the last decode lives
 struct FrameLoc {
-  bool foreign = false;  // in the arena of padded planes, not in its legacy slot
   long long off[3] = {0, 0, 0};  // first int16 / sample byte of each component's plane
-  long long pix = 0;     // first byte of its pixels (legacy: d_pix, else f_pix)
+  long long pix = 0;             // first byte of its pixels
 };
 
+// The order a component's blocks were coded in, hence its DC prediction:
+// inside an MCU of hs x vs blocks left-right, top-bottom, MCUs in raster
+// order, the prediction starting again every seg blocks.  A one-component
+// scan is a 1x1 scan of MCUs one block wide that never resets.
+struct ScanGeom {
+  int hs, vs, mcus_x, seg;
+};
+
+ScanGeom scan_geom(const Parsed &P, int c) {
+  const int nb = P.bw[c] * P.bh[c];
+  if (!P.interleaved) return {1, 1, P.bw[c], nb};
+  const long long seg = P.ri ? std::min<long long>((long long)P.ri * P.hs[c] * P.vs[c], nb) : nb;
+  return {P.hs[c], P.vs[c], P.mcus_x, (int)seg};
+}
+
+// at least `need` elements, and `floor` of them at the first allocation
 template <class T>
-int grow(T *&p, size_t &cap, size_t need) {
+int grow(T *&p, size_t &cap, size_t need, size_t floor = 0) {
   if (need <= cap) return MIJ_OK;
   hipFree(p);  // waits for the device
   p = nullptr;
   cap = 0;
+  need = std::max(need, floor);
   HIP_TRY(hipMalloc((void **)&p, need * sizeof(T)));
   cap = need;
   return MIJ_OK;
@@ -1314,67 +979,49 @@ struct mij_decoder {
   int max_w = 0, max_h = 0, cap = 0;
   size_t blob_cap = 0;
   uint8_t *d_blob = nullptr, *h_blob = nullptr;
-  int16_t *d_coef = nullptr;
   mij::DecTab *d_tabs = nullptr;
-  mij::DecJob *d_jobs = nullptr;
-  int *d_status = nullptr;
   int *d_changed = nullptr;
   long long *d_entry = nullptr, *d_exit[2] = {nullptr, nullptr}, *d_base = nullptr;
   int *d_nblk = nullptr;
-  int chunk_cap = 0, job_cap = 1 << 30, last_passes = 0;
+  int chunk_cap = 0, last_passes = 0;
   std::vector<Parsed> parsed;
   std::vector<FrameLoc> loc;
-  long long plane_px = 0;  // max_w * max_h: Y plane; Cb/Cr a quarter each
   int n = 0;
-  // pixels (mij_decoder_reconstruct): allocated on its first call
-  bool rec_ready = false;  // the legacy frames' buffers exist
-  bool rec_valid = false;  // they hold the last decode's frames
+  // One arena for every frame: planes padded to whole MCUs (the encoder's
+  // shape has no padding), packed frame after frame in the order of the call.
+  // A buffer's first allocation takes what max_frames frames of max_w x max_h
+  // of the encoder's shape need (the coefficients' at create, the others' at
+  // first use); it grows (is freed and allocated again) only when a call's
+  // padded planes need more, so a decoder that only sees the encoder's
+  // streams never reallocates.
+  int16_t *d_coef = nullptr;
   uint8_t *d_planes = nullptr, *d_pix = nullptr;
   int32_t *d_dc = nullptr, *d_recq = nullptr;
   uint32_t *d_tile = nullptr;
+  mij::DecIvl *d_jobs = nullptr;
+  mij::DecScan *d_scans = nullptr;
+  int *d_status = nullptr;
   mij::RecJob *d_rjobs = nullptr;
-  mij::RecFrame *d_rframes = nullptr;
-  std::vector<mij::RecJob> h_rjobs;  // kept: the uploads are asynchronous
-  std::vector<mij::RecFrame> h_rframes;
+  mij::RecPix *d_rpix = nullptr;
+  size_t d_coef_cap = 0, d_planes_cap = 0, d_pix_cap = 0, d_dc_cap = 0, d_recq_cap = 0, d_tile_cap = 0,
+         d_jobs_cap = 0, d_scans_cap = 0, d_status_cap = 0, d_rjobs_cap = 0, d_rpix_cap = 0;
+  long long pix_bytes = 0;  // of the last decode's frames
+  // pixels (mij_decoder_reconstruct / _scaled)
+  bool rec_valid = false;  // the planes and pixels are the last decode's
+  int rec_denom = 1;       // of the last reconstruct
+  std::vector<mij::ScaledGeom> sgeom;  // per frame, of the last reconstruct
+  std::vector<mij::RecJob> h_rjobs;    // kept: the uploads are asynchronous
+  std::vector<mij::RecPix> h_rpix;
   std::vector<int32_t> h_recq;
   hipEvent_t rec_ev[3] = {nullptr, nullptr, nullptr};
-  // Frames that are not of the legacy shape live in an arena of their own,
-  // packed frame after frame in the order of the call and grown (freed and
-  // allocated again) when a call needs more: a decoder that only ever sees
-  // legacy streams allocates none of it.
-  int16_t *f_coef = nullptr;
-  uint8_t *f_planes = nullptr, *f_pix = nullptr;
-  int32_t *f_dc = nullptr, *f_recq = nullptr;
-  uint32_t *f_tile = nullptr;
-  mij::IlJob *f_jobs = nullptr;
-  mij::IlFrame *f_frames = nullptr;
-  int *f_status = nullptr;
-  mij::IlRec *f_rjobs = nullptr;
-  mij::IlPix *f_rpix = nullptr;
-  size_t f_coef_cap = 0, f_planes_cap = 0, f_pix_cap = 0, f_dc_cap = 0, f_recq_cap = 0, f_tile_cap = 0,
-         f_jobs_cap = 0, f_frames_cap = 0, f_status_cap = 0, f_rjobs_cap = 0, f_rpix_cap = 0;
-  long long f_pix_bytes = 0;  // of the last decode's frames
-  std::vector<mij::IlRec> h_irec;
-  std::vector<mij::IlPix> h_ipix;
-  std::vector<int32_t> h_irecq;
-  // decoding at 1/2, 1/4, 1/8 scale (mij_decoder_reconstruct_scaled, DESIGN.md
-  // §4j): the job tables only; planes and pixels take the places of the
-  // full-size ones
-  int rec_denom = 1;  // of the last reconstruct
-  std::vector<mij::ScaledGeom> sgeom;  // per frame, when rec_denom > 1
-  mij::ScJob *s_jobs = nullptr;
-  mij::IlPix *s_pix = nullptr;
-  size_t s_jobs_cap = 0, s_pix_cap = 0;
-  std::vector<mij::ScJob> h_sjobs;
-  std::vector<mij::IlPix> h_spix;
   // lossless transcoding (mij_decoder_transcode): everything allocated at its
   // first call and grown like the arena.  It keeps its own DC prefix sums, so
   // that it and reconstruct may run in either order, or alone.
   bool tc_valid = false;  // the streams below are the last decode's
   hipEvent_t tc_ev[2] = {nullptr, nullptr};
-  int32_t *t_dcl = nullptr, *t_dcf = nullptr;  // prefix sums of the legacy slots' / the arena's DCs
+  int32_t *t_dc = nullptr;  // prefix sums of the arena's DCs
   uint32_t *t_tile = nullptr;
-  mij::IlRec *t_rec = nullptr;
+  mij::RecJob *t_rec = nullptr;
   mij::TcDc *t_dcjobs = nullptr;
   int16_t *t_abs = nullptr;
   mij::TcFrame *t_frames = nullptr;
@@ -1388,11 +1035,11 @@ struct mij_decoder {
   int *t_hdr = nullptr, *t_err = nullptr;
   uint8_t *t_out = nullptr;
   uint64_t *t_len = nullptr;
-  size_t t_dcl_cap = 0, t_dcf_cap = 0, t_tile_cap = 0, t_rec_cap = 0, t_dcjobs_cap = 0, t_abs_cap = 0,
-         t_frames_cap = 0, t_outs_cap = 0, t_hist_cap = 0, t_ehuf_cap = 0, t_hc_cap = 0, t_blk_bits_cap = 0,
-         t_mcu_off_cap = 0, t_row_bits_cap = 0, t_row_pre_cap = 0, t_ival_cap = 0, t_row_off_cap = 0,
-         t_bits_cap = 0, t_raw_cap = 0, t_ffc_cap = 0, t_hdr_cap = 0, t_err_cap = 0, t_out_cap = 0, t_len_cap = 0;
-  std::vector<mij::IlRec> h_trec;  // kept: the uploads are asynchronous
+  size_t t_dc_cap = 0, t_tile_cap = 0, t_rec_cap = 0, t_dcjobs_cap = 0, t_abs_cap = 0, t_frames_cap = 0,
+         t_outs_cap = 0, t_hist_cap = 0, t_ehuf_cap = 0, t_hc_cap = 0, t_blk_bits_cap = 0, t_mcu_off_cap = 0,
+         t_row_bits_cap = 0, t_row_pre_cap = 0, t_ival_cap = 0, t_row_off_cap = 0, t_bits_cap = 0, t_raw_cap = 0,
+         t_ffc_cap = 0, t_hdr_cap = 0, t_err_cap = 0, t_out_cap = 0, t_len_cap = 0;
+  std::vector<mij::RecJob> h_trec;  // kept: the uploads are asynchronous
   std::vector<mij::TcDc> h_tdc;
   std::vector<mij::TcFrame> h_tframes;
   std::vector<mij::TcOut> h_touts;
@@ -1404,49 +1051,26 @@ struct mij_decoder {
   mij::XfFrame *x_frames = nullptr;
   size_t x_plane_cap = 0, x_abs_cap = 0, x_frames_cap = 0;
   std::vector<mij::XfFrame> h_xframes;
+  // what max_frames frames of max_w x max_h of the encoder's shape take: int16
+  // coefficients == sample bytes, and components == scans
+  size_t floor_units() const { return (size_t)cap * max_w * max_h * 3 / 2; }
+  size_t floor_comps() const { return (size_t)cap * 3; }
 };
 
 static void decoder_free(mij_decoder *d) {
   if (!d) return;
   hipSetDevice(d->dev);
   if (d->stream) hipStreamSynchronize(d->stream);
-  hipFree(d->d_blob);
-  hipFree(d->d_coef);
-  hipFree(d->d_tabs);
-  hipFree(d->d_jobs);
-  hipFree(d->d_status);
-  hipFree(d->d_changed);
-  hipFree(d->d_entry);
-  hipFree(d->d_exit[0]);
-  hipFree(d->d_exit[1]);
-  hipFree(d->d_nblk);
-  hipFree(d->d_base);
-  hipFree(d->d_planes);
-  hipFree(d->d_pix);
-  hipFree(d->d_dc);
-  hipFree(d->d_recq);
-  hipFree(d->d_tile);
-  hipFree(d->d_rjobs);
-  hipFree(d->d_rframes);
-  hipFree(d->f_coef);
-  hipFree(d->f_planes);
-  hipFree(d->f_pix);
-  hipFree(d->f_dc);
-  hipFree(d->f_recq);
-  hipFree(d->f_tile);
-  hipFree(d->f_jobs);
-  hipFree(d->f_frames);
-  hipFree(d->f_status);
-  hipFree(d->f_rjobs);
-  hipFree(d->f_rpix);
-  hipFree(d->s_jobs);
-  hipFree(d->s_pix);
-  for (void *p : {(void *)d->t_dcl, (void *)d->t_dcf, (void *)d->t_tile, (void *)d->t_rec, (void *)d->t_dcjobs,
-                  (void *)d->t_abs, (void *)d->t_frames, (void *)d->t_outs, (void *)d->t_hist, (void *)d->t_ehuf,
-                  (void *)d->t_hc, (void *)d->t_blk_bits, (void *)d->t_mcu_off, (void *)d->t_row_bits,
-                  (void *)d->t_row_pre, (void *)d->t_ival, (void *)d->t_row_off, (void *)d->t_bits, (void *)d->t_raw,
-                  (void *)d->t_ffc, (void *)d->t_hdr, (void *)d->t_err, (void *)d->t_out, (void *)d->t_len,
-                  (void *)d->x_plane, (void *)d->x_abs, (void *)d->x_frames})
+  for (void *p : {(void *)d->d_blob, (void *)d->d_tabs, (void *)d->d_changed, (void *)d->d_entry, (void *)d->d_exit[0],
+                  (void *)d->d_exit[1], (void *)d->d_nblk, (void *)d->d_base, (void *)d->d_coef, (void *)d->d_planes,
+                  (void *)d->d_pix, (void *)d->d_dc, (void *)d->d_recq, (void *)d->d_tile, (void *)d->d_jobs,
+                  (void *)d->d_scans, (void *)d->d_status, (void *)d->d_rjobs, (void *)d->d_rpix, (void *)d->t_dc,
+                  (void *)d->t_tile, (void *)d->t_rec, (void *)d->t_dcjobs, (void *)d->t_abs, (void *)d->t_frames,
+                  (void *)d->t_outs, (void *)d->t_hist, (void *)d->t_ehuf, (void *)d->t_hc, (void *)d->t_blk_bits,
+                  (void *)d->t_mcu_off, (void *)d->t_row_bits, (void *)d->t_row_pre, (void *)d->t_ival,
+                  (void *)d->t_row_off, (void *)d->t_bits, (void *)d->t_raw, (void *)d->t_ffc, (void *)d->t_hdr,
+                  (void *)d->t_err, (void *)d->t_out, (void *)d->t_len, (void *)d->x_plane, (void *)d->x_abs,
+                  (void *)d->x_frames})
     hipFree(p);
   for (hipEvent_t e : d->rec_ev)
     if (e) hipEventDestroy(e);
@@ -1473,14 +1097,11 @@ extern "C" mij_decoder *mij_decoder_create(int device, int max_w, int max_h, int
   d->max_w = max_w;
   d->max_h = max_h;
   d->cap = max_frames;
-  d->plane_px = (long long)max_w * max_h;
   auto init = [&]() -> int {
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-    HIP_TRY(hipMalloc((void **)&d->d_coef, (size_t)max_frames * d->plane_px * 3 / 2 * sizeof(int16_t)));
+    if (int rc = grow(d->d_coef, d->d_coef_cap, 1, d->floor_units())) return rc;
     HIP_TRY(hipMalloc((void **)&d->d_tabs, (size_t)max_frames * 4 * sizeof(mij::DecTab)));
-    HIP_TRY(hipMalloc((void **)&d->d_jobs, (size_t)max_frames * 3 * sizeof(mij::DecJob)));
-    HIP_TRY(hipMalloc((void **)&d->d_status, (size_t)max_frames * 3 * sizeof(int)));
     HIP_TRY(hipMalloc((void **)&d->d_changed, sizeof(int)));
     return MIJ_OK;
   };
@@ -1521,8 +1142,8 @@ static size_t unstuff(uint8_t *dst, const uint8_t *s, size_t b, size_t e) {
   return o;
 }
 
-static int decoder_buffers(mij_decoder *d, int nchunks, int njobs) {
-  if (nchunks <= d->chunk_cap && njobs <= d->job_cap) return MIJ_OK;
+static int decoder_buffers(mij_decoder *d, int nchunks) {
+  if (nchunks <= d->chunk_cap) return MIJ_OK;
   // null each pointer once freed: a failed hipMalloc below must not leave
   // one dangling for the next call or decoder_free to free again
   for (void **p : {(void **)&d->d_entry, (void **)&d->d_exit[0], (void **)&d->d_exit[1], (void **)&d->d_nblk,
@@ -1541,94 +1162,74 @@ static int decoder_buffers(mij_decoder *d, int nchunks, int njobs) {
   return MIJ_OK;
 }
 
-// the legacy frames' scans: jobs[3 * i + k] belongs to frame leg[i]
-static int decode_legacy(mij_decoder *d, std::vector<mij::DecJob> &jobs, const std::vector<int> &leg, int *passes_out) {
-  int nchunks = 0, max_chunks = 1;
-  for (auto &j : jobs) {
-    j.chunk0 = nchunks;
-    nchunks += j.nchunks;
-    max_chunks = std::max(max_chunks, j.nchunks);
-  }
-  const int nj = (int)jobs.size();
-  HIP_TRY(hipMemcpyAsync(d->d_jobs, jobs.data(), jobs.size() * sizeof(mij::DecJob), hipMemcpyHostToDevice,
-                         d->stream));
-  HIP_TRY(hipMemsetAsync(d->d_status, 0, nj * sizeof(int), d->stream));
-  mij::SyncArgs a{d->d_blob, d->d_jobs, nj, nchunks, d->d_tabs, d->d_entry, d->d_exit[1], d->d_exit[0],
-                  d->d_nblk, d->d_changed, 1};
-  const dim3 grid((nchunks + 255) / 256);
-  hipLaunchKernelGGL(mij::k_dec_sync, grid, dim3(256), 0, d->stream, a);
-  HIP_TRY(hipGetLastError());
-  int cur = 0, passes = 1;
-  for (;; passes++) {
-    // every pass settles at least one more chunk of each scan, so this bound
-    // is never reached by a valid stream (badly synchronising content, e.g.
-    // Q=100 noise with blocks longer than a chunk, only costs more passes)
-    if (passes > max_chunks + 1) return mij_fail(MIJ_EJPEG, "decoder: chunk states did not settle");
-    HIP_TRY(hipMemsetAsync(d->d_changed, 0, sizeof(int), d->stream));
-    a.first = 0;
-    a.exit_in = d->d_exit[cur];
-    a.exit_out = d->d_exit[!cur];
-    hipLaunchKernelGGL(mij::k_dec_sync, grid, dim3(256), 0, d->stream, a);
-    HIP_TRY(hipGetLastError());
-    cur = !cur;
-    int changed = 0;
-    HIP_TRY(hipMemcpyAsync(&changed, d->d_changed, sizeof(int), hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipStreamSynchronize(d->stream));
-    if (!changed) break;
-  }
-  *passes_out = passes;
-  hipLaunchKernelGGL(mij::k_dec_scan, dim3(nj), dim3(256), 0, d->stream, d->d_jobs, d->d_nblk, d->d_base,
-                     d->d_status);
-  hipLaunchKernelGGL(mij::k_dec_write, grid, dim3(256), 0, d->stream, a, d->d_base, d->d_coef, d->d_status);
-  HIP_TRY(hipGetLastError());
-  std::vector<int> st(nj);
-  HIP_TRY(hipMemcpyAsync(st.data(), d->d_status, nj * sizeof(int), hipMemcpyDeviceToHost, d->stream));
-  HIP_TRY(hipStreamSynchronize(d->stream));
-  for (int j = 0; j < nj; j++)
-    if (st[j]) return mij_fail(MIJ_EJPEG, "stream %d scan %d: corrupt entropy data (%d)", leg[j / 3], j % 3, st[j]);
-  return MIJ_OK;
-}
+// which stream a scan belongs to, for the error text
+struct ScanId {
+  int stream;
+  int scan;  // of a stream of one-component scans; -1: the stream's interleaved scan
+};
 
-// the other frames' restart intervals; their chunk arrays start at chunk `c0`
-// of the decoder's (behind the legacy scans')
-static int decode_interleaved(mij_decoder *d, std::vector<mij::IlJob> &jobs, std::vector<mij::IlFrame> &frames,
-                              const std::vector<int> &fgn, int c0, int *passes_out) {
-  const int nj = (int)jobs.size(), nf = (int)frames.size();
-  int nchunks = 0, max_chunks = 1;
+// Every scan of the call: assigns the chunks, uploads the intervals and the
+// scans, runs the passes until the chunk states settle, then the prefix sums
+// and the writing pass.
+static int decode_scans(mij_decoder *d, std::vector<mij::DecIvl> &jobs, std::vector<mij::DecScan> &scans,
+                        const std::vector<ScanId> &ids) {
+  const int nj = (int)jobs.size(), ns = (int)scans.size();
+  // chunks [0, n1): the scans of one-block MCUs (k_dec_sync / k_dec_write <true>), then the others
+  std::stable_partition(jobs.begin(), jobs.end(), [&](const mij::DecIvl &j) { return scans[j.scan].bpm == 1; });
+  int nchunks = 0, n1 = 0, max_chunks = 1;
   for (auto &j : jobs) {
-    mij::IlFrame &F = frames[j.frame];
-    if (F.nchunks == 0) F.chunk0 = nchunks;
+    mij::DecScan &S = scans[j.scan];
+    if (S.nchunks == 0) S.chunk0 = nchunks;
     j.chunk0 = nchunks;
     nchunks += j.nchunks;
-    F.nchunks += j.nchunks;
+    S.nchunks += j.nchunks;
     max_chunks = std::max(max_chunks, j.nchunks);
+    if (S.bpm == 1) n1 = nchunks;
   }
-  if (int rc = grow(d->f_jobs, d->f_jobs_cap, (size_t)nj)) return rc;
-  if (int rc = grow(d->f_frames, d->f_frames_cap, (size_t)nf)) return rc;
-  if (int rc = grow(d->f_status, d->f_status_cap, (size_t)nf)) return rc;
-  HIP_TRY(hipMemcpyAsync(d->f_jobs, jobs.data(), nj * sizeof(mij::IlJob), hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(hipMemcpyAsync(d->f_frames, frames.data(), nf * sizeof(mij::IlFrame), hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(hipMemsetAsync(d->f_status, 0, nf * sizeof(int), d->stream));
-  mij::IlArgs a{d->d_blob, d->f_jobs, d->f_frames, nj, nchunks, d->d_tabs, d->d_entry + c0, d->d_exit[1] + c0,
-                d->d_exit[0] + c0, d->d_nblk + c0, d->d_changed, 1};
-  const dim3 grid((nchunks + 255) / 256);
-  hipLaunchKernelGGL(mij::k_il_sync, grid, dim3(256), 0, d->stream, a);
+  bool any_il = false;  // an interleaved scan (a greyscale file's included) sets the passes' policy below
+  for (const ScanId &id : ids) any_il |= id.scan < 0;
+  if (int rc = decoder_buffers(d, nchunks)) return rc;
+  if (int rc = grow(d->d_jobs, d->d_jobs_cap, (size_t)nj, d->floor_comps())) return rc;
+  if (int rc = grow(d->d_scans, d->d_scans_cap, (size_t)ns, d->floor_comps())) return rc;
+  if (int rc = grow(d->d_status, d->d_status_cap, (size_t)ns, d->floor_comps())) return rc;
+  HIP_TRY(hipMemcpyAsync(d->d_jobs, jobs.data(), nj * sizeof(mij::DecIvl), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->d_scans, scans.data(), ns * sizeof(mij::DecScan), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemsetAsync(d->d_status, 0, ns * sizeof(int), d->stream));
+  mij::DecArgs a{d->d_blob, d->d_jobs, d->d_scans, nj, 0, 0, d->d_tabs, d->d_entry, d->d_exit[1], d->d_exit[0],
+                 d->d_nblk, d->d_changed, 1};
+  // one launch per kind of chunk that the call holds
+  auto both = [&](auto one, auto others, auto... more) {
+    if (n1) {
+      a.chunk0 = 0, a.chunk1 = n1;
+      hipLaunchKernelGGL(one, dim3((n1 + 255) / 256), dim3(256), 0, d->stream, a, more...);
+    }
+    if (n1 < nchunks) {
+      a.chunk0 = n1, a.chunk1 = nchunks;
+      hipLaunchKernelGGL(others, dim3((nchunks - n1 + 255) / 256), dim3(256), 0, d->stream, a, more...);
+    }
+  };
+  both(mij::k_dec_sync<true>, mij::k_dec_sync<false>);
   HIP_TRY(hipGetLastError());
   int cur = 0, passes = 1;
   for (;;) {
-    // as above: each pass settles one more chunk of every interval.  The
-    // slot makes interleaved scans settle later than one-component scans (a
+    // Every pass settles at least one more chunk of each interval, so the
+    // bound below is never reached by a valid stream (badly synchronising
+    // content, e.g. Q=100 noise with blocks longer than a chunk, only costs
+    // more passes).  One-component scans settle in 2-3 passes and the host
+    // looks after each.  The slot makes interleaved scans settle later (a
     // chunk may find the right bit and the wrong luma slot, which only the
     // next chroma block exposes), and a pass in which nothing changes costs
-    // little, so after the first two the host looks only every fourth pass.
-    const int group = passes < 3 ? 1 : 4;
-    if (passes > max_chunks + 1 + group) return mij_fail(MIJ_EJPEG, "decoder: chunk states did not settle");
+    // little, so with such a scan in the call the host looks only every
+    // fourth pass after the first two.
+    const int group = any_il && passes >= 3 ? 4 : 1;
+    if (passes > max_chunks + 1 + (any_il ? group : 0))
+      return mij_fail(MIJ_EJPEG, "decoder: chunk states did not settle");
     HIP_TRY(hipMemsetAsync(d->d_changed, 0, sizeof(int), d->stream));
     a.first = 0;
     for (int g = 0; g < group; g++, passes++) {
-      a.exit_in = d->d_exit[cur] + c0;
-      a.exit_out = d->d_exit[!cur] + c0;
-      hipLaunchKernelGGL(mij::k_il_sync, grid, dim3(256), 0, d->stream, a);
+      a.exit_in = d->d_exit[cur];
+      a.exit_out = d->d_exit[!cur];
+      both(mij::k_dec_sync<true>, mij::k_dec_sync<false>);
       cur = !cur;
     }
     HIP_TRY(hipGetLastError());
@@ -1637,15 +1238,20 @@ static int decode_interleaved(mij_decoder *d, std::vector<mij::IlJob> &jobs, std
     HIP_TRY(hipStreamSynchronize(d->stream));
     if (!changed) break;
   }
-  *passes_out = passes;
-  hipLaunchKernelGGL(mij::k_il_scan, dim3(nf), dim3(256), 0, d->stream, d->f_frames, d->d_nblk + c0, d->d_base + c0);
-  hipLaunchKernelGGL(mij::k_il_write, grid, dim3(256), 0, d->stream, a, d->d_base + c0, d->f_coef, d->f_status);
+  // (a call of one-component scans alone has always reported its passes
+  // without the last, which only confirms)
+  d->last_passes = any_il ? passes : passes - 1;
+  hipLaunchKernelGGL(mij::k_dec_scan, dim3(ns), dim3(256), 0, d->stream, d->d_scans, d->d_nblk, d->d_base);
+  both(mij::k_dec_write<true>, mij::k_dec_write<false>, d->d_base, d->d_coef, d->d_status);
   HIP_TRY(hipGetLastError());
-  std::vector<int> st(nf);
-  HIP_TRY(hipMemcpyAsync(st.data(), d->f_status, nf * sizeof(int), hipMemcpyDeviceToHost, d->stream));
+  std::vector<int> st(ns);
+  HIP_TRY(hipMemcpyAsync(st.data(), d->d_status, ns * sizeof(int), hipMemcpyDeviceToHost, d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
-  for (int j = 0; j < nf; j++)
-    if (st[j]) return mij_fail(MIJ_EJPEG, "stream %d: corrupt entropy data (%d)", fgn[j], st[j]);
+  for (int s = 0; s < ns; s++) {
+    if (!st[s]) continue;
+    if (ids[s].scan < 0) return mij_fail(MIJ_EJPEG, "stream %d: corrupt entropy data (%d)", ids[s].stream, st[s]);
+    return mij_fail(MIJ_EJPEG, "stream %d scan %d: corrupt entropy data (%d)", ids[s].stream, ids[s].scan, st[s]);
+  }
   return MIJ_OK;
 }
 
@@ -1676,15 +1282,13 @@ extern "C" int mij_decoder_decode(mij_decoder *d, const uint8_t *const *jpgs, co
   for (int f = 0; f < n; f++)
     if (!jpgs[f]) return mij_fail(MIJ_EINVAL, "decoder_decode: stream %d is NULL", f);
   parallel([&](int f) { prc[f] = parse(jpgs[f], lens[f], d->parsed[f], f); });
-  std::vector<int> leg, fgn;  // frames of either kind
   for (int f = 0; f < n; f++) {
     if (prc[f]) return mij_fail(prc[f], "decoder_decode: %s", d->parsed[f].err);
     const Parsed &P = d->parsed[f];
     if (P.w > d->max_w || P.h > d->max_h)
       return mij_fail(MIJ_EINVAL, "stream %d: %dx%d exceeds the decoder's %dx%d", f, P.w, P.h, d->max_w, d->max_h);
-    (P.legacy ? leg : fgn).push_back(f);
   }
-  // pieces (a legacy scan, or one restart interval): raw length + >= 16 zero
+  // pieces (a one-component scan, or one restart interval): raw length + >= 16 zero
   // bytes, 8-aligned
   struct Piece {
     size_t at, next;
@@ -1702,39 +1306,29 @@ extern "C" int mij_decoder_decode(mij_decoder *d, const uint8_t *const *jpgs, co
       pieces.push_back({off, next, b, e, 0});
       off = next;
     };
-    if (P.legacy)
-      for (int k = 0; k < 3; k++) add(P.scan[k].data, P.scan[k].end);
-    else
+    if (P.interleaved)
       for (const auto &iv : P.ivl) add(iv.data, iv.end);
+    else
+      for (int k = 0; k < 3; k++) add(P.scan[k].data, P.scan[k].end);
   }
   piece0[n] = pieces.size();
   // chunk ids are ints: every piece has max(1, ceil(bits / 512)) chunks
   if (off / 64 + pieces.size() > 0x7fff0000u) return mij_fail(MIJ_EINVAL, "decoder_decode: too much entropy data");
   if (int rc = decoder_stage(d, off)) return rc;
-  // the arena of the frames that are not of the legacy shape
-  const long long fs = d->plane_px * 3 / 2;  // int16 per legacy frame slot
+  // the arena: every frame's padded planes and pixels, back to back
   long long units = 0, pixb = 0;
   for (int f = 0; f < n; f++) {
     const Parsed &P = d->parsed[f];
     FrameLoc &L = d->loc[f];
-    if (P.legacy) {
-      const long long ny = (long long)P.w * P.h;
-      L.off[0] = f * fs;
-      L.off[1] = f * fs + ny;
-      L.off[2] = f * fs + ny + ny / 4;
-      L.pix = f * d->plane_px * 3;
-    } else {
-      L.foreign = true;
-      for (int c = 0; c < P.ncomp; c++) {
-        L.off[c] = units;
-        units += 64LL * P.bw[c] * P.bh[c];
-      }
-      L.pix = pixb;
-      pixb += P.pitch() * P.h;
+    for (int c = 0; c < P.ncomp; c++) {
+      L.off[c] = units;
+      units += 64LL * P.bw[c] * P.bh[c];
     }
+    L.pix = pixb;
+    pixb += P.pitch() * P.h;
   }
-  d->f_pix_bytes = pixb;
-  if (int rc = grow(d->f_coef, d->f_coef_cap, (size_t)units)) return rc;
+  d->pix_bytes = pixb;
+  if (int rc = grow(d->d_coef, d->d_coef_cap, (size_t)units, d->floor_units())) return rc;
   std::vector<mij::DecTab> tabs(4 * (size_t)n);
   parallel([&](int f) {
     const Parsed &P = d->parsed[f];
@@ -1746,80 +1340,63 @@ extern "C" int mij_decoder_decode(mij_decoder *d, const uint8_t *const *jpgs, co
     }
   });
   auto chunks_of = [](long long nbits) { return std::max(1, (int)((nbits + mij::CHUNK - 1) / mij::CHUNK)); };
-  std::vector<mij::DecJob> jobs(3 * leg.size());
-  for (size_t i = 0; i < leg.size(); i++) {
-    const int f = leg[i];
+  // one scan per stream, or its three one-component scans; one interval per piece
+  std::vector<mij::DecScan> scans;
+  std::vector<mij::DecIvl> jobs;
+  std::vector<ScanId> ids;
+  for (int f = 0; f < n; f++) {
     const Parsed &P = d->parsed[f];
-    const long long ny = (long long)P.w * P.h;
-    for (int k = 0; k < 3; k++) {
-      const auto &sc = P.scan[k];
-      const Piece &pc = pieces[piece0[f] + k];
-      mij::DecJob &j = jobs[3 * i + k];
-      j.data = (long long)pc.at;
-      j.nbits = 8LL * (long long)pc.len;
-      j.out = d->loc[f].off[sc.comp];
-      j.nblocks = (int)(sc.comp ? ny / 256 : ny / 64);
-      j.dc = 4 * f + 2 * sc.td;
-      j.ac = 4 * f + 2 * sc.ta + 1;
-      j.nchunks = chunks_of(j.nbits);
+    const int nscans = P.interleaved ? 1 : 3;
+    for (int k = 0; k < nscans; k++) {
+      mij::DecScan S;
+      memset(&S, 0, sizeof S);
+      const int c0 = P.interleaved ? 0 : P.scan[k].comp;  // the scan's first component
+      S.ncomp = P.interleaved ? P.ncomp : 1;
+      for (int i = 0; i < S.ncomp; i++) {
+        const int c = c0 + i;
+        const ScanGeom g = scan_geom(P, c);
+        S.off[i] = d->loc[f].off[c];
+        S.hs[i] = g.hs;
+        S.vs[i] = g.vs;
+        S.bw[i] = P.bw[c];
+        S.mcus_x = g.mcus_x;
+        S.nmcus = P.bw[c] * P.bh[c] / (g.hs * g.vs);
+        S.dc[i] = 4 * f + 2 * (P.interleaved ? P.td[c] : P.scan[k].td);
+        S.ac[i] = 4 * f + 2 * (P.interleaved ? P.ta[c] : P.scan[k].ta) + 1;
+        for (int y = 0; y < g.vs; y++)
+          for (int x = 0; x < g.hs; x++) {  // at most 2 * 2 + 1 + 1 = 6: parse() admits no other sampling
+            S.slot_comp[S.bpm] = i;
+            S.slot_x[S.bpm] = x;
+            S.slot_y[S.bpm] = y;
+            S.bpm++;
+          }
+      }
+      const int ri = P.ri ? P.ri : S.nmcus;  // (parse() admits no DRI before one-component scans)
+      const size_t p0 = piece0[f] + (P.interleaved ? 0 : k), np = P.interleaved ? P.ivl.size() : 1;
+      for (size_t i = 0; i < np; i++) {
+        const Piece &pc = pieces[p0 + i];
+        mij::DecIvl j;
+        j.data = (long long)pc.at;
+        j.nbits = 8LL * (long long)pc.len;
+        j.scan = (int)scans.size();
+        // parse() made the interval count ceil(nmcus / ri), so mcu0 < nmcus and
+        // mcu0 + nmcus_i <= nmcus: what bounds k_dec_write's stores
+        j.mcu0 = (int)((long long)i * ri);
+        j.nmcus = std::min(ri, S.nmcus - j.mcu0);
+        j.chunk0 = 0;
+        j.nchunks = chunks_of(j.nbits);
+        j.pad = 0;
+        if (j.mcu0 >= S.nmcus || j.nmcus < 1) return mij_fail(MIJ_EJPEG, "stream %d: restart interval %zu has no MCUs", f, i);
+        jobs.push_back(j);
+      }
+      scans.push_back(S);
+      ids.push_back({f, P.interleaved ? -1 : k});
     }
   }
-  std::vector<mij::IlFrame> iframes(fgn.size());
-  std::vector<mij::IlJob> ijobs;
-  for (size_t i = 0; i < fgn.size(); i++) {
-    const int f = fgn[i];
-    const Parsed &P = d->parsed[f];
-    mij::IlFrame &F = iframes[i];
-    memset(&F, 0, sizeof F);
-    F.ncomp = P.ncomp;
-    F.mcus_x = P.mcus_x;
-    F.nmcus = P.mcus_x * P.mcus_y;
-    for (int c = 0; c < P.ncomp; c++) {
-      F.off[c] = d->loc[f].off[c];
-      F.hs[c] = P.hs[c];
-      F.vs[c] = P.vs[c];
-      F.bw[c] = P.bw[c];
-      F.dc[c] = 4 * f + 2 * P.td[c];
-      F.ac[c] = 4 * f + 2 * P.ta[c] + 1;
-      for (int y = 0; y < P.vs[c]; y++)
-        for (int x = 0; x < P.hs[c]; x++) {  // at most 2 * 2 + 1 + 1 = 6: parse() admits no other sampling
-          F.slot_comp[F.bpm] = c;
-          F.slot_x[F.bpm] = x;
-          F.slot_y[F.bpm] = y;
-          F.bpm++;
-        }
-    }
-    const int ri = P.ri ? P.ri : F.nmcus;
-    for (size_t k = 0; k < P.ivl.size(); k++) {
-      const Piece &pc = pieces[piece0[f] + k];
-      mij::IlJob j;
-      j.data = (long long)pc.at;
-      j.nbits = 8LL * (long long)pc.len;
-      j.frame = (int)i;
-      // parse() made the interval count ceil(nmcus / ri), so mcu0 < nmcus and
-      // mcu0 + nmcus_i <= nmcus: what bounds k_il_write's stores
-      j.mcu0 = (int)((long long)k * ri);
-      j.nmcus = std::min(ri, F.nmcus - j.mcu0);
-      j.chunk0 = 0;
-      j.nchunks = chunks_of(j.nbits);
-      j.pad = 0;
-      if (j.mcu0 >= F.nmcus || j.nmcus < 1) return mij_fail(MIJ_EJPEG, "stream %d: restart interval %zu has no MCUs", f, k);
-      ijobs.push_back(j);
-    }
-  }
-  long long nch_leg = 0, nch_il = 0;
-  for (auto &j : jobs) nch_leg += j.nchunks;
-  for (auto &j : ijobs) nch_il += j.nchunks;
-  if (int rc = decoder_buffers(d, (int)(nch_leg + nch_il), 0)) return rc;
   HIP_TRY(hipMemcpyAsync(d->d_blob, d->h_blob, off, hipMemcpyHostToDevice, d->stream));
   HIP_TRY(hipMemcpyAsync(d->d_tabs, tabs.data(), tabs.size() * sizeof(mij::DecTab), hipMemcpyHostToDevice,
                          d->stream));
-  int p1 = 0, p2 = 0;
-  if (!leg.empty())
-    if (int rc = decode_legacy(d, jobs, leg, &p1)) return rc;
-  if (!fgn.empty())
-    if (int rc = decode_interleaved(d, ijobs, iframes, fgn, (int)nch_leg, &p2)) return rc;
-  d->last_passes = std::max(p1, p2);
+  if (int rc = decode_scans(d, jobs, scans, ids)) return rc;
   d->n = n;
   return MIJ_OK;
 }
@@ -1857,16 +1434,16 @@ extern "C" int mij_decoder_layout(mij_decoder *d, int frame, int *out, int n) {
 extern "C" int mij_decoder_coefs(mij_decoder *d, int frame, int16_t *Y, int16_t *Cb, int16_t *Cr) {
   mij_clear_error();
   if (!d || frame < 0 || frame >= d->n || !Y || !Cb || !Cr) return mij_fail(MIJ_EINVAL, "decoder_coefs: bad args");
-  if (d->loc[frame].foreign)
+  const Parsed &P = d->parsed[frame];
+  if (!P.legacy)
     return mij_fail(MIJ_EINVAL, "decoder_coefs: frame %d is not of the encoder's layout; use mij_decoder_layout and "
                     "mij_decoder_component", frame);
   HIP_TRY(hipSetDevice(d->dev));
-  const Parsed &P = d->parsed[frame];
   const long long ny = (long long)P.w * P.h;
-  const int16_t *src = d->d_coef + frame * (d->plane_px * 3 / 2);
-  HIP_TRY(hipMemcpyAsync(Y, src, ny * 2, hipMemcpyDeviceToHost, d->stream));
-  HIP_TRY(hipMemcpyAsync(Cb, src + ny, ny / 2, hipMemcpyDeviceToHost, d->stream));
-  HIP_TRY(hipMemcpyAsync(Cr, src + ny + ny / 4, ny / 2, hipMemcpyDeviceToHost, d->stream));
+  const long long *off = d->loc[frame].off;
+  HIP_TRY(hipMemcpyAsync(Y, d->d_coef + off[0], ny * 2, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipMemcpyAsync(Cb, d->d_coef + off[1], ny / 2, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipMemcpyAsync(Cr, d->d_coef + off[2], ny / 2, hipMemcpyDeviceToHost, d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
   return MIJ_OK;
 }
@@ -1883,14 +1460,11 @@ extern "C" int mij_decoder_component(mij_decoder *d, int frame, int comp, int16_
   const long long nb = (long long)P.bw[comp] * P.bh[comp];
   if (cap < (size_t)(64 * nb)) return mij_fail(MIJ_ENOSPC, "decoder_component: need %lld coefficients", 64 * nb);
   HIP_TRY(hipSetDevice(d->dev));
-  const FrameLoc &L = d->loc[frame];
-  const int16_t *src = (L.foreign ? d->f_coef : d->d_coef) + L.off[comp];
-  HIP_TRY(hipMemcpyAsync(dst, src, (size_t)(128 * nb), hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipMemcpyAsync(dst, d->d_coef + d->loc[frame].off[comp], (size_t)(128 * nb), hipMemcpyDeviceToHost,
+                         d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
-  // legacy: a one-component scan predicts in raster order, never resets
-  const int hs = L.foreign ? P.hs[comp] : 1, vs = L.foreign ? P.vs[comp] : 1;
-  const int mx_n = P.bw[comp] / hs;
-  const long long seg = L.foreign && P.ri ? (long long)P.ri * hs * vs : nb;
+  const ScanGeom g = scan_geom(P, comp);
+  const int hs = g.hs, vs = g.vs, mx_n = g.mcus_x, seg = g.seg;
   uint32_t run = 0;
   for (long long s = 0; s < nb; s++) {
     const long long m = s / (hs * vs), i = s % (hs * vs);
@@ -1905,53 +1479,20 @@ extern "C" int mij_decoder_component(mij_decoder *d, int frame, int comp, int16_
 
 extern "C" void *mij_decoder_device_coefs(mij_decoder *d, int frame) {
   if (!d || frame < 0 || frame >= d->n) return nullptr;
-  const FrameLoc &L = d->loc[frame];
-  return (L.foreign ? d->f_coef : d->d_coef) + L.off[0];
+  return d->d_coef + d->loc[frame].off[0];
 }
 
 // ---------------------------------------------------------------------------
 // pixels: host side
 // ---------------------------------------------------------------------------
-static int decoder_rec_buffers(mij_decoder *d, bool legacy) {
-  for (hipEvent_t &e : d->rec_ev)
-    if (!e) HIP_TRY(hipEventCreate(&e));
-  if (d->rec_ready || !legacy) return MIJ_OK;
-  const size_t fs = (size_t)d->plane_px * 3 / 2, cap = (size_t)d->cap;
-  auto alloc = [&]() -> int {
-    HIP_TRY(hipMalloc((void **)&d->d_planes, cap * fs));
-    HIP_TRY(hipMalloc((void **)&d->d_pix, cap * (size_t)d->plane_px * 3));
-    HIP_TRY(hipMalloc((void **)&d->d_dc, cap * (fs / 64) * sizeof(int32_t)));
-    HIP_TRY(hipMalloc((void **)&d->d_recq, cap * 128 * sizeof(int32_t)));
-    // tiles: a plane of b blocks has at most b / DC_TILE + 1
-    HIP_TRY(hipMalloc((void **)&d->d_tile, cap * (fs / 64 / mij::DC_TILE + 3) * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&d->d_rjobs, cap * 3 * sizeof(mij::RecJob)));
-    HIP_TRY(hipMalloc((void **)&d->d_rframes, cap * sizeof(mij::RecFrame)));
-    return MIJ_OK;
-  };
-  if (int rc = alloc()) {  // all or nothing: the next call starts over
-    for (void **p : {(void **)&d->d_planes, (void **)&d->d_pix, (void **)&d->d_dc, (void **)&d->d_recq,
-                     (void **)&d->d_tile, (void **)&d->d_rjobs, (void **)&d->d_rframes}) {
-      hipFree(*p);
-      *p = nullptr;
-    }
-    return rc;
-  }
-  d->rec_ready = true;
-  return MIJ_OK;
+static void scaled_geom(const Parsed &P, int denom, mij::ScaledGeom &G) {
+  mij::scaled_geometry(P.w, P.h, P.ncomp, P.hs, P.vs, P.bw, P.bh, denom, G);
 }
 
-static int pix_mode(const Parsed &P) {
-  if (P.ncomp == 1) return mij::PIX_GREY;
-  if (P.hmax == 1) return mij::PIX_444;
-  const bool rep = (P.w + 1) / 2 <= 2;  // libjpeg: fancy only for downsampled_width > 2
-  if (P.vmax == 1) return rep ? mij::PIX_H2V1_REP : mij::PIX_H2V1;
-  return rep ? mij::PIX_H2V2_REP : mij::PIX_H2V2;
-}
-
-static int reconstruct_scaled_launch(mij_decoder *d, int order, int denom);
-
-// denom 1: full size; 2, 4, 8: DESIGN.md §4j
-static int reconstruct_any(mij_decoder *d, int order, int denom) {
+// denom 1: full size; 2, 4, 8: DESIGN.md §4j.  The absolute DCs, then every
+// component through the IDCT of the size scaled_geometry gives it, then the
+// colour stage on that geometry.
+static int reconstruct(mij_decoder *d, int order, int denom) {
   mij_clear_error();
   if (!d) return mij_fail(MIJ_EINVAL, "decoder_reconstruct: no decoder");
   if (order != MIJ_PIX_BGR && order != MIJ_PIX_RGB)
@@ -1960,298 +1501,119 @@ static int reconstruct_any(mij_decoder *d, int order, int denom) {
     return mij_fail(MIJ_EINVAL, "decoder_reconstruct_scaled: scale 1/%d: 1/1, 1/2, 1/4 or 1/8", denom);
   if (d->n < 1) return mij_fail(MIJ_EINVAL, "decoder_reconstruct: no decoded frames");
   HIP_TRY(hipSetDevice(d->dev));
-  const int n = d->n;
-  int nl = 0, nf = 0;
-  for (int f = 0; f < n; f++) (d->loc[f].foreign ? nf : nl)++;
-  if (int rc = decoder_rec_buffers(d, nl > 0)) return rc;
-  // the previous call's uploads read these vectors: let them finish first
+  for (hipEvent_t &e : d->rec_ev)
+    if (!e) HIP_TRY(hipEventCreate(&e));
+  // the previous call's uploads read the vectors below: let them finish first
   HIP_TRY(hipStreamSynchronize(d->stream));
   d->rec_valid = false;
-  d->h_rjobs.resize(3 * (size_t)nl);
-  d->h_rframes.resize(nl);
-  d->h_recq.resize(128 * (size_t)n);
-  long long idct_wgs = 0, col_wgs = 0, tiles = 0;
-  int li = 0;
-  for (int f = 0; f < n; f++) {
-    const Parsed &P = d->parsed[f];
-    if (d->loc[f].foreign) continue;
-    if (!P.have_dqt[P.tq[0]] || !P.have_dqt[P.tq[1]]) return mij_fail(MIJ_EJPEG, "stream %d: DQT missing", f);
-    for (int t = 0; t < 2; t++)
-      for (int z = 0; z < 64; z++) d->h_recq[128 * f + 64 * t + z] = P.dqt[P.tq[t]][z];
-    const long long ny = (long long)P.w * P.h;
-    for (int c = 0; c < 3; c++) {
-      mij::RecJob &j = d->h_rjobs[3 * li + c];
-      j.off = d->loc[f].off[c];
-      j.nblocks = (int)(c ? ny / 256 : ny / 64);
-      j.bw = c ? P.w / 16 : P.w / 8;
-      j.wg0 = (int)idct_wgs;
-      j.qt = 2 * f + (c != 0);
-      j.tile0 = (int)tiles;
-      j.pad = 0;
-      idct_wgs += (j.nblocks + 255) / 256;
-      tiles += (j.nblocks + mij::DC_TILE - 1) / mij::DC_TILE;
-    }
-    mij::RecFrame &fr = d->h_rframes[li++];
-    fr.planes = d->loc[f].off[0];
-    fr.pix = d->loc[f].pix;
-    fr.w = P.w;
-    fr.h = P.h;
-    fr.wg0 = (int)col_wgs;
-    fr.pad = 0;
-    col_wgs += ((long long)(P.h / 2) * (P.w / 16) + 255) / 256;
-  }
-  // the frames in the arena: one IlRec per component, one IlPix per frame
-  d->h_irec.clear();
-  d->h_ipix.clear();
-  d->h_irecq.clear();
-  long long i_wgs = 0, i_col = 0, i_tiles = 0, units = 0;
-  for (int f = 0; f < n; f++) {
-    const Parsed &P = d->parsed[f];
-    const FrameLoc &L = d->loc[f];
-    if (!L.foreign) continue;
-    for (int c = 0; c < P.ncomp; c++) {
-      mij::IlRec j;
-      j.off = L.off[c];
-      j.nblocks = P.bw[c] * P.bh[c];
-      j.bw = P.bw[c];
-      j.wg0 = (int)i_wgs;
-      j.qt = (int)(d->h_irecq.size() / 64);
-      j.tile0 = (int)i_tiles;
-      j.hs = P.hs[c];
-      j.vs = P.vs[c];
-      j.mcus_x = P.mcus_x;
-      j.seg = P.ri ? (int)std::min<long long>((long long)P.ri * P.hs[c] * P.vs[c], j.nblocks) : j.nblocks;
-      j.pad = 0;
-      for (int z = 0; z < 64; z++) d->h_irecq.push_back(P.dqt[P.tq[c]][z]);
-      i_wgs += (j.nblocks + 255) / 256;
-      i_tiles += (j.nblocks + mij::DC_TILE - 1) / mij::DC_TILE;
-      units = std::max(units, j.off + 64LL * j.nblocks);
-      d->h_irec.push_back(j);
-    }
-    mij::IlPix px;
-    memset(&px, 0, sizeof px);
-    px.y = L.off[0];
-    px.cb = L.off[P.ncomp > 1 ? 1 : 0];
-    px.cr = L.off[P.ncomp > 1 ? 2 : 0];
-    px.pix = L.pix;
-    px.G.w = P.w;
-    px.G.h = P.h;
-    px.G.mode = pix_mode(P);
-    px.G.yp = 8 * P.bw[0];
-    px.G.cp = P.ncomp > 1 ? 8 * P.bw[1] : 8 * P.bw[0];
-    px.G.cw = (P.w + P.hmax - 1) / P.hmax;
-    px.G.ch = (P.h + P.vmax - 1) / P.vmax;
-    px.G.pitch = P.pitch();
-    px.groups = (P.w + 15) / 16;
-    const int rows = mij::pix_rows_per_lane(px.G.mode);
-    px.units = (P.h + rows - 1) / rows;
-    px.wg0 = (int)i_col;
-    i_col += ((long long)px.units * px.groups + 255) / 256;
-    d->h_ipix.push_back(px);
-  }
-  if (idct_wgs > 0x7fffffff || col_wgs > 0x7fffffff || i_wgs > 0x7fffffff || i_col > 0x7fffffff)
-    return mij_fail(MIJ_EINVAL, "decoder_reconstruct: too many blocks");
-  if (nf) {
-    if (int rc = grow(d->f_planes, d->f_planes_cap, (size_t)units)) return rc;
-    if (int rc = grow(d->f_dc, d->f_dc_cap, (size_t)(units / 64))) return rc;
-    if (int rc = grow(d->f_tile, d->f_tile_cap, (size_t)i_tiles)) return rc;
-    if (int rc = grow(d->f_pix, d->f_pix_cap, (size_t)d->f_pix_bytes)) return rc;
-    if (int rc = grow(d->f_recq, d->f_recq_cap, d->h_irecq.size())) return rc;
-    if (int rc = grow(d->f_rjobs, d->f_rjobs_cap, d->h_irec.size())) return rc;
-    if (int rc = grow(d->f_rpix, d->f_rpix_cap, d->h_ipix.size())) return rc;
-    HIP_TRY(hipMemcpyAsync(d->f_rjobs, d->h_irec.data(), d->h_irec.size() * sizeof(mij::IlRec), hipMemcpyHostToDevice,
-                           d->stream));
-    HIP_TRY(hipMemcpyAsync(d->f_rpix, d->h_ipix.data(), d->h_ipix.size() * sizeof(mij::IlPix), hipMemcpyHostToDevice,
-                           d->stream));
-    HIP_TRY(hipMemcpyAsync(d->f_recq, d->h_irecq.data(), d->h_irecq.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                           d->stream));
-  }
-  if (nl) {
-    HIP_TRY(hipMemcpyAsync(d->d_rjobs, d->h_rjobs.data(), d->h_rjobs.size() * sizeof(mij::RecJob),
-                           hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(d->d_rframes, d->h_rframes.data(), d->h_rframes.size() * sizeof(mij::RecFrame),
-                           hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(d->d_recq, d->h_recq.data(), d->h_recq.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                           d->stream));
-  }
-  const int nir = (int)d->h_irec.size();
-  if (denom > 1) {  // the same DC kernels, then the scaled IDCTs and the colour stage on the scaled geometry
-    if (int rc = reconstruct_scaled_launch(d, order, denom)) return rc;
-    d->rec_denom = denom;
-    d->rec_valid = true;
-    return MIJ_OK;
-  }
-  HIP_TRY(hipEventRecord(d->rec_ev[0], d->stream));
-  if (nl) {
-    hipLaunchKernelGGL(mij::k_dec_dc, dim3((unsigned)tiles), dim3(mij::DC_T), 0, d->stream, d->d_rjobs, 3 * nl,
-                       d->d_coef, d->d_dc, d->d_tile);
-    hipLaunchKernelGGL(mij::k_dec_dcbase<mij::RecJob>, dim3((3 * nl + 63) / 64), dim3(64), 0, d->stream, d->d_rjobs,
-                       3 * nl, d->d_tile);
-    hipLaunchKernelGGL(mij::k_dec_idct, dim3((unsigned)idct_wgs), dim3(256), 0, d->stream, d->d_rjobs, 3 * nl,
-                       d->d_coef, d->d_dc, d->d_tile, d->d_recq, d->d_planes);
-  }
-  if (nf) {
-    hipLaunchKernelGGL(mij::k_il_dc, dim3((unsigned)i_tiles), dim3(mij::DC_T), 0, d->stream, d->f_rjobs, nir,
-                       d->f_coef, d->f_dc, d->f_tile);
-    hipLaunchKernelGGL(mij::k_dec_dcbase<mij::IlRec>, dim3((nir + 63) / 64), dim3(64), 0, d->stream, d->f_rjobs, nir,
-                       d->f_tile);
-    hipLaunchKernelGGL(mij::k_il_idct, dim3((unsigned)i_wgs), dim3(256), 0, d->stream, d->f_rjobs, nir, d->f_coef,
-                       d->f_dc, d->f_tile, d->f_recq, d->f_planes);
-  }
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(d->rec_ev[1], d->stream));
-  if (nl)
-    hipLaunchKernelGGL(mij::k_dec_colour, dim3((unsigned)col_wgs), dim3(256), 0, d->stream, d->d_rframes, nl,
-                       d->d_planes, d->d_pix, order == MIJ_PIX_RGB);
-  if (nf)
-    hipLaunchKernelGGL(mij::k_il_colour, dim3((unsigned)i_col), dim3(256), 0, d->stream, d->f_rpix, nf, d->f_planes,
-                       d->f_pix, order == MIJ_PIX_RGB);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(d->rec_ev[2], d->stream));
-  d->rec_denom = 1;
-  d->rec_valid = true;
-  return MIJ_OK;
-}
-
-static void scaled_geom(const Parsed &P, int denom, mij::ScaledGeom &G) {
-  mij::scaled_geometry(P.w, P.h, P.ncomp, P.hs, P.vs, P.bw, P.bh, denom, G);
-}
-
-// reconstruct_any's second half at 1/2, 1/4, 1/8: d->h_rjobs / h_irec are
-// built and on their way to the device, the buffers exist
-static int reconstruct_scaled_launch(mij_decoder *d, int order, int denom) {
   const int n = d->n;
   d->sgeom.resize(n);
-  // ScJobs in eight runs: legacy frames' then the arena's, each by IDCT size 8, 4, 2, 1
-  std::vector<mij::ScJob> run[2][4];
-  long long wgs[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, col[2] = {0, 0};
-  std::vector<mij::IlPix> pix[2];
-  int li = 0, ir = 0;
+  d->h_recq.clear();
+  d->h_rpix.clear();
+  // the components' jobs in five runs: IDCT size 8 with the raster DC rule, then sizes 8, 4, 2, 1
+  std::vector<mij::RecJob> run[5];
+  long long wgs[5] = {0, 0, 0, 0, 0}, col = 0, units = 0, tiles = 0;
   for (int f = 0; f < n; f++) {
     const Parsed &P = d->parsed[f];
     const FrameLoc &L = d->loc[f];
     mij::ScaledGeom &G = d->sgeom[f];
     scaled_geom(P, denom, G);
-    const int set = L.foreign ? 1 : 0;
     for (int c = 0; c < P.ncomp; c++) {
-      mij::ScJob j;
+      if (!P.have_dqt[P.tq[c]]) return mij_fail(MIJ_EJPEG, "stream %d: DQT missing", f);
+      const ScanGeom g = scan_geom(P, c);
+      mij::RecJob j;
       memset(&j, 0, sizeof j);
       j.off = L.off[c];
       j.bw = P.bw[c];
       j.bh = P.bh[c];
       j.nblocks = P.bw[c] * P.bh[c];
-      if (L.foreign) {
-        const mij::IlRec &r = d->h_irec[ir++];
-        j.qt = r.qt;
-        j.tile0 = r.tile0;
-        j.hs = r.hs;
-        j.vs = r.vs;
-        j.mcus_x = r.mcus_x;
-        j.seg = r.seg;
-        j.il = 1;
-      } else {
-        const mij::RecJob &r = d->h_rjobs[3 * li + c];
-        j.qt = r.qt;
-        j.tile0 = r.tile0;
-        j.hs = j.vs = j.mcus_x = j.seg = 1;
-      }
-      const int S = G.c[c].S, k = S == 8 ? 0 : S == 4 ? 1 : S == 2 ? 2 : 3;
+      j.qt = (int)(d->h_recq.size() / 64);
+      for (int z = 0; z < 64; z++) d->h_recq.push_back(P.dqt[P.tq[c]][z]);
+      j.hs = g.hs;
+      j.vs = g.vs;
+      j.mcus_x = g.mcus_x;
+      j.seg = g.seg;
+      // raster: the scan order is the plane's raster order and the DCs never reset
+      const bool raster = g.hs * g.vs == 1 && g.seg >= j.nblocks;
+      const int S = G.c[c].S, k = S == 8 ? (raster ? 0 : 1) : S == 4 ? 2 : S == 2 ? 3 : 4;
       j.pitch = G.c[c].pitch;
       j.spr = G.c[c].pitch / 8;
-      j.wg0 = (int)wgs[set][k];
-      wgs[set][k] += ((long long)j.bh * j.spr + 32 * S - 1) / (32 * S);  // 256 * S / 8 strips per workgroup
-      run[set][k].push_back(j);
+      j.wg0 = (int)wgs[k];
+      wgs[k] += ((long long)j.bh * j.spr + 32 * S - 1) / (32 * S);  // 256 * S / 8 strips per workgroup
+      units = std::max(units, j.off + 64LL * j.nblocks);
+      run[k].push_back(j);
     }
-    if (!L.foreign) li++;
-    mij::IlPix px;
+    mij::RecPix px;
     memset(&px, 0, sizeof px);
     px.y = L.off[0];
     px.cb = L.off[P.ncomp > 1 ? 1 : 0];
     px.cr = L.off[P.ncomp > 1 ? 2 : 0];
     px.pix = L.pix;
-    px.G.w = G.ow;
-    px.G.h = G.oh;
-    px.G.mode = G.mode;
-    px.G.yp = G.c[0].pitch;
-    px.G.cp = G.c[1].pitch;
-    px.G.cw = G.c[1].cw;
-    px.G.ch = G.c[1].ch;
-    px.G.pitch = (3LL * G.ow + 15) / 16 * 16;
+    px.G = mij::pix_geometry(G);
     px.groups = (G.ow + 15) / 16;
     const int rows = mij::pix_rows_per_lane(G.mode);
     px.units = (G.oh + rows - 1) / rows;
-    px.wg0 = (int)col[set];
-    col[set] += ((long long)px.units * px.groups + 255) / 256;
-    pix[set].push_back(px);
+    px.wg0 = (int)col;
+    col += ((long long)px.units * px.groups + 255) / 256;
+    d->h_rpix.push_back(px);
   }
-  d->h_sjobs.clear();
-  d->h_spix.clear();
-  size_t first[2][4], pfirst[2];
-  for (int set = 0; set < 2; set++) {
-    for (int k = 0; k < 4; k++) {
-      if (wgs[set][k] > 0x7fffffff) return mij_fail(MIJ_EINVAL, "decoder_reconstruct_scaled: too many blocks");
-      first[set][k] = d->h_sjobs.size();
-      d->h_sjobs.insert(d->h_sjobs.end(), run[set][k].begin(), run[set][k].end());
+  // one table: k_dec_dc walks all of it, so the tiles are numbered along it
+  d->h_rjobs.clear();
+  size_t first[5];
+  for (int k = 0; k < 5; k++) {
+    first[k] = d->h_rjobs.size();
+    for (mij::RecJob &j : run[k]) {
+      j.tile0 = (int)tiles;
+      tiles += (j.nblocks + mij::DC_TILE - 1) / mij::DC_TILE;
+      d->h_rjobs.push_back(j);
     }
-    if (col[set] > 0x7fffffff) return mij_fail(MIJ_EINVAL, "decoder_reconstruct_scaled: too many blocks");
-    pfirst[set] = d->h_spix.size();
-    d->h_spix.insert(d->h_spix.end(), pix[set].begin(), pix[set].end());
+    if (wgs[k] > 0x7fffffff) return mij_fail(MIJ_EINVAL, "decoder_reconstruct: too many blocks");
   }
-  if (int rc = grow(d->s_jobs, d->s_jobs_cap, d->h_sjobs.size())) return rc;
-  if (int rc = grow(d->s_pix, d->s_pix_cap, d->h_spix.size())) return rc;
-  HIP_TRY(hipMemcpyAsync(d->s_jobs, d->h_sjobs.data(), d->h_sjobs.size() * sizeof(mij::ScJob), hipMemcpyHostToDevice,
-                         d->stream));
-  HIP_TRY(hipMemcpyAsync(d->s_pix, d->h_spix.data(), d->h_spix.size() * sizeof(mij::IlPix), hipMemcpyHostToDevice,
+  if (col > 0x7fffffff || tiles > 0x7fffffff) return mij_fail(MIJ_EINVAL, "decoder_reconstruct: too many blocks");
+  const int nj = (int)d->h_rjobs.size();
+  const size_t fu = d->floor_units(), fc = d->floor_comps();
+  if (int rc = grow(d->d_planes, d->d_planes_cap, (size_t)units, fu)) return rc;
+  if (int rc = grow(d->d_dc, d->d_dc_cap, (size_t)(units / 64), fu / 64)) return rc;
+  // tiles: a plane of b blocks has at most b / DC_TILE + 1
+  if (int rc = grow(d->d_tile, d->d_tile_cap, (size_t)tiles, fu / 64 / mij::DC_TILE + fc)) return rc;
+  if (int rc = grow(d->d_pix, d->d_pix_cap, (size_t)d->pix_bytes, 2 * fu)) return rc;
+  if (int rc = grow(d->d_recq, d->d_recq_cap, d->h_recq.size(), 64 * fc)) return rc;
+  if (int rc = grow(d->d_rjobs, d->d_rjobs_cap, (size_t)nj, fc)) return rc;
+  if (int rc = grow(d->d_rpix, d->d_rpix_cap, (size_t)n, (size_t)d->cap)) return rc;
+  HIP_TRY(hipMemcpyAsync(d->d_rjobs, d->h_rjobs.data(), nj * sizeof(mij::RecJob), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->d_rpix, d->h_rpix.data(), n * sizeof(mij::RecPix), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->d_recq, d->h_recq.data(), d->h_recq.size() * sizeof(int32_t), hipMemcpyHostToDevice,
                          d->stream));
   HIP_TRY(hipEventRecord(d->rec_ev[0], d->stream));
-  const int nl = (int)pix[0].size(), nf = (int)pix[1].size(), nir = (int)d->h_irec.size();
-  if (nl) {
-    const mij::RecJob &last = d->h_rjobs.back();
-    const int tiles = last.tile0 + (last.nblocks + mij::DC_TILE - 1) / mij::DC_TILE;
-    hipLaunchKernelGGL(mij::k_dec_dc, dim3((unsigned)tiles), dim3(mij::DC_T), 0, d->stream, d->d_rjobs, 3 * nl,
-                       d->d_coef, d->d_dc, d->d_tile);
-    hipLaunchKernelGGL(mij::k_dec_dcbase<mij::RecJob>, dim3((3 * nl + 63) / 64), dim3(64), 0, d->stream, d->d_rjobs,
-                       3 * nl, d->d_tile);
-  }
-  if (nf) {
-    const mij::IlRec &last = d->h_irec.back();
-    const int tiles = last.tile0 + (last.nblocks + mij::DC_TILE - 1) / mij::DC_TILE;
-    hipLaunchKernelGGL(mij::k_il_dc, dim3((unsigned)tiles), dim3(mij::DC_T), 0, d->stream, d->f_rjobs, nir, d->f_coef,
-                       d->f_dc, d->f_tile);
-    hipLaunchKernelGGL(mij::k_dec_dcbase<mij::IlRec>, dim3((nir + 63) / 64), dim3(64), 0, d->stream, d->f_rjobs, nir,
-                       d->f_tile);
-  }
-  for (int set = 0; set < 2; set++) {
-    const int16_t *coefs = set ? d->f_coef : d->d_coef;
-    const int32_t *dc = set ? d->f_dc : d->d_dc, *q = set ? d->f_recq : d->d_recq;
-    const uint32_t *tile = set ? d->f_tile : d->d_tile;
-    uint8_t *planes = set ? d->f_planes : d->d_planes;
-#define SC_LAUNCH(S, k)                                                                                           \
-  if (wgs[set][k])                                                                                                \
-    hipLaunchKernelGGL(mij::k_sc_idct<S>, dim3((unsigned)wgs[set][k]), dim3(256), 0, d->stream,                   \
-                       d->s_jobs + first[set][k], (int)run[set][k].size(), coefs, dc, tile, q, planes)
-    SC_LAUNCH(8, 0);
-    SC_LAUNCH(4, 1);
-    SC_LAUNCH(2, 2);
-    SC_LAUNCH(1, 3);
-#undef SC_LAUNCH
-  }
+  hipLaunchKernelGGL(mij::k_dec_dc, dim3((unsigned)tiles), dim3(mij::DC_T), 0, d->stream, d->d_rjobs, nj, d->d_coef,
+                     d->d_dc, d->d_tile);
+  hipLaunchKernelGGL(mij::k_dec_dcbase, dim3((nj + 63) / 64), dim3(64), 0, d->stream, d->d_rjobs, nj, d->d_tile);
+#define IDCT_LAUNCH(S, R, k)                                                                                \
+  if (wgs[k])                                                                                               \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(mij::k_dec_idct<S, R>), dim3((unsigned)wgs[k]), dim3(256), 0, d->stream, \
+                       d->d_rjobs + first[k], (int)run[k].size(), d->d_coef, d->d_dc, d->d_tile, d->d_recq,  \
+                       d->d_planes)
+  IDCT_LAUNCH(8, true, 0);
+  IDCT_LAUNCH(8, false, 1);
+  IDCT_LAUNCH(4, false, 2);
+  IDCT_LAUNCH(2, false, 3);
+  IDCT_LAUNCH(1, false, 4);
+#undef IDCT_LAUNCH
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(d->rec_ev[1], d->stream));
-  for (int set = 0; set < 2; set++)
-    if (col[set])
-      hipLaunchKernelGGL(mij::k_il_colour, dim3((unsigned)col[set]), dim3(256), 0, d->stream, d->s_pix + pfirst[set],
-                         (int)pix[set].size(), set ? d->f_planes : d->d_planes, set ? d->f_pix : d->d_pix,
-                         order == MIJ_PIX_RGB);
+  hipLaunchKernelGGL(mij::k_dec_colour, dim3((unsigned)col), dim3(256), 0, d->stream, d->d_rpix, n, d->d_planes,
+                     d->d_pix, order == MIJ_PIX_RGB);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(d->rec_ev[2], d->stream));
+  d->rec_denom = denom;
+  d->rec_valid = true;
   return MIJ_OK;
 }
 
-extern "C" int mij_decoder_reconstruct(mij_decoder *d, int order) { return reconstruct_any(d, order, 1); }
+extern "C" int mij_decoder_reconstruct(mij_decoder *d, int order) { return reconstruct(d, order, 1); }
 
 extern "C" int mij_decoder_reconstruct_scaled(mij_decoder *d, int order, int denom) {
-  return reconstruct_any(d, order, denom);
+  return reconstruct(d, order, denom);
 }
 
 extern "C" int mij_decoder_scaled_layout(mij_decoder *d, int frame, int denom, int *out, int n) {
@@ -2285,16 +1647,9 @@ static int rec_frame(mij_decoder *d, int frame, const char *what, const Parsed *
 
 // size and device pitch of the frame's pixels as the last reconstruct left them
 static void rec_size(const mij_decoder *d, int frame, int *w, int *h, long long *pitch) {
-  const Parsed &P = d->parsed[frame];
-  if (d->rec_denom > 1) {
-    *w = d->sgeom[frame].ow;
-    *h = d->sgeom[frame].oh;
-    *pitch = (3LL * *w + 15) / 16 * 16;
-  } else {
-    *w = P.w;
-    *h = P.h;
-    *pitch = d->loc[frame].foreign ? P.pitch() : 3LL * P.w;  // legacy widths: 3 * w is a multiple of 16 already
-  }
+  *w = d->sgeom[frame].ow;
+  *h = d->sgeom[frame].oh;
+  *pitch = mij::pix_geometry(d->sgeom[frame]).pitch;
 }
 
 extern "C" int mij_decoder_pixels(mij_decoder *d, int frame, uint8_t *dst, size_t cap, long long pitch) {
@@ -2311,10 +1666,8 @@ extern "C" int mij_decoder_pixels(mij_decoder *d, int frame, uint8_t *dst, size_
   const unsigned long long need = (unsigned long long)(h - 1) * pitch + row;
   if (cap < need) return mij_fail(MIJ_ENOSPC, "decoder_pixels: need %llu bytes", need);
   HIP_TRY(hipSetDevice(d->dev));
-  const FrameLoc &L = d->loc[frame];
-  const uint8_t *src = (L.foreign ? d->f_pix : d->d_pix) + L.pix;
-  HIP_TRY(hipMemcpy2DAsync(dst, (size_t)pitch, src, (size_t)dpitch, (size_t)row, h, hipMemcpyDeviceToHost,
-                           d->stream));
+  HIP_TRY(hipMemcpy2DAsync(dst, (size_t)pitch, d->d_pix + d->loc[frame].pix, (size_t)dpitch, (size_t)row, h,
+                           hipMemcpyDeviceToHost, d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
   return MIJ_OK;
 }
@@ -2327,15 +1680,15 @@ extern "C" int mij_decoder_planes(mij_decoder *d, int frame, uint8_t *Y, uint8_t
   if (d->rec_denom > 1)
     return mij_fail(MIJ_EINVAL, "decoder_planes: the last reconstruct was at 1/%d scale; use mij_decoder_scaled_layout "
                     "and mij_decoder_plane", d->rec_denom);
-  if (d->loc[frame].foreign)
+  if (!P->legacy)
     return mij_fail(MIJ_EINVAL, "decoder_planes: frame %d is not of the encoder's layout; use mij_decoder_layout and "
                     "mij_decoder_plane", frame);
   HIP_TRY(hipSetDevice(d->dev));
   const long long ny = (long long)P->w * P->h;
-  const uint8_t *src = d->d_planes + frame * (d->plane_px * 3 / 2);
-  HIP_TRY(hipMemcpyAsync(Y, src, ny, hipMemcpyDeviceToHost, d->stream));
-  HIP_TRY(hipMemcpyAsync(Cb, src + ny, ny / 4, hipMemcpyDeviceToHost, d->stream));
-  HIP_TRY(hipMemcpyAsync(Cr, src + ny + ny / 4, ny / 4, hipMemcpyDeviceToHost, d->stream));
+  const long long *off = d->loc[frame].off;
+  HIP_TRY(hipMemcpyAsync(Y, d->d_planes + off[0], ny, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipMemcpyAsync(Cb, d->d_planes + off[1], ny / 4, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipMemcpyAsync(Cr, d->d_planes + off[2], ny / 4, hipMemcpyDeviceToHost, d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
   return MIJ_OK;
 }
@@ -2346,13 +1699,10 @@ extern "C" int mij_decoder_plane(mij_decoder *d, int frame, int comp, uint8_t *d
   if (int rc = rec_frame(d, frame, "decoder_plane", &P)) return rc;
   if (!dst) return mij_fail(MIJ_EINVAL, "decoder_plane: dst is NULL");
   if (comp < 0 || comp >= P->ncomp) return mij_fail(MIJ_EINVAL, "decoder_plane: component %d of %d", comp, P->ncomp);
-  size_t nbytes = (size_t)64 * P->bw[comp] * P->bh[comp];
-  if (d->rec_denom > 1) nbytes = (size_t)d->sgeom[frame].c[comp].pitch * d->sgeom[frame].c[comp].rows;
+  const size_t nbytes = (size_t)d->sgeom[frame].c[comp].pitch * d->sgeom[frame].c[comp].rows;
   if (cap < nbytes) return mij_fail(MIJ_ENOSPC, "decoder_plane: need %zu bytes", nbytes);
   HIP_TRY(hipSetDevice(d->dev));
-  const FrameLoc &L = d->loc[frame];
-  HIP_TRY(hipMemcpyAsync(dst, (L.foreign ? d->f_planes : d->d_planes) + L.off[comp], nbytes, hipMemcpyDeviceToHost,
-                         d->stream));
+  HIP_TRY(hipMemcpyAsync(dst, d->d_planes + d->loc[frame].off[comp], nbytes, hipMemcpyDeviceToHost, d->stream));
   HIP_TRY(hipStreamSynchronize(d->stream));
   return MIJ_OK;
 }
@@ -2361,12 +1711,11 @@ extern "C" void *mij_decoder_device_pixels(mij_decoder *d, int frame, long long 
   mij_clear_error();
   const Parsed *P;
   if (rec_frame(d, frame, "decoder_device_pixels", &P)) return nullptr;
-  const FrameLoc &L = d->loc[frame];
   int w, h;
   long long dpitch;
   rec_size(d, frame, &w, &h, &dpitch);
   if (pitch) *pitch = dpitch;
-  return (L.foreign ? d->f_pix : d->d_pix) + L.pix;
+  return d->d_pix + d->loc[frame].pix;
 }
 
 extern "C" int mij_decoder_reconstruct_ms(mij_decoder *d, float ms[2]) {
@@ -2487,8 +1836,8 @@ static int tc_run(mij_decoder *d, int restart_rows, const XfPlan *plans, bool xf
   // sizes of the per-call arrays
   // (src_nblk: the decoded planes' blocks; nblk, nmcu, nrows: the output's,
   // never more than the source's)
-  long long src_nblk = 0, nblk = 0, nmcu = 0, nrows = 0, dcl = 0, dcf = 0, tiles_l = 0, tiles_f = 0;
-  int ncl = 0, ncf = 0, max_nblk = 0, max_rows = 0, max_comp = 0;
+  long long src_nblk = 0, nblk = 0, nmcu = 0, nrows = 0, ndc = 0, tiles = 0;
+  int ncomp = 0, max_nblk = 0, max_rows = 0, max_comp = 0;
   for (int f = 0; f < n; f++) {
     const Parsed &P = d->parsed[f];
     const FrameLoc &L = d->loc[f];
@@ -2498,9 +1847,9 @@ static int tc_run(mij_decoder *d, int restart_rows, const XfPlan *plans, bool xf
       const long long nb = (long long)P.bw[c] * P.bh[c];
       src_nblk += nb;
       fb += (long long)X.bw[c] * X.bh[c];
-      (L.foreign ? dcf : dcl) = std::max(L.foreign ? dcf : dcl, L.off[c] / 64 + nb);
-      (L.foreign ? tiles_f : tiles_l) += (nb + mij::DC_TILE - 1) / mij::DC_TILE;
-      (L.foreign ? ncf : ncl)++;
+      ndc = std::max(ndc, L.off[c] / 64 + nb);
+      tiles += (nb + mij::DC_TILE - 1) / mij::DC_TILE;
+      ncomp++;
       max_comp = (int)std::max<long long>(max_comp, nb);
     }
     nblk += fb;
@@ -2510,12 +1859,10 @@ static int tc_run(mij_decoder *d, int restart_rows, const XfPlan *plans, bool xf
     max_rows = std::max(max_rows, X.mcus_y);
   }
   if (src_nblk > 0x7fff0000LL) return mij_fail(MIJ_EINVAL, "%s: too many blocks", who);
-  const int ncomp = ncl + ncf;
 #define TC_GROW(p, cnt)                                            \
   if (int rc = grow(d->p, d->p##_cap, (size_t)(cnt))) return rc
-  TC_GROW(t_dcl, dcl);
-  TC_GROW(t_dcf, dcf);
-  TC_GROW(t_tile, tiles_l + tiles_f);
+  TC_GROW(t_dc, ndc);
+  TC_GROW(t_tile, tiles);
   TC_GROW(t_rec, ncomp);
   TC_GROW(t_dcjobs, ncomp);
   TC_GROW(t_abs, src_nblk);
@@ -2540,14 +1887,12 @@ static int tc_run(mij_decoder *d, int restart_rows, const XfPlan *plans, bool xf
   TC_GROW(t_hdr, n);
   TC_GROW(t_err, n);
   TC_GROW(t_len, n);
-  // descriptors: the legacy frames' components first (k_il_dc runs once over
-  // each of the two coefficient buffers), a legacy plane as a 1x1 scan of
-  // MCUs one block wide that never resets
-  d->h_trec.assign(ncomp, mij::IlRec());
+  // descriptors: of a RecJob only what k_dec_dc and k_dec_dcbase read
+  d->h_trec.assign(ncomp, mij::RecJob());
   d->h_tdc.assign(ncomp, mij::TcDc());
   d->h_tframes.assign(n, mij::TcFrame());
-  int il = 0, ifg = ncl;
-  long long tl = 0, tf = 0, ab = 0, xb = 0, b0 = 0, m0 = 0, r0 = 0;
+  int k = 0;
+  long long t0 = 0, ab = 0, xb = 0, b0 = 0, m0 = 0, r0 = 0;
   for (int f = 0; f < n; f++) {
     const Parsed &P = d->parsed[f];
     const FrameLoc &L = d->loc[f];
@@ -2571,23 +1916,22 @@ static int tc_run(mij_decoder *d, int restart_rows, const XfPlan *plans, bool xf
       d->h_xframes[f].ncomp = P.ncomp;
     }
     bool used[4] = {false, false, false, false};
-    for (int c = 0; c < P.ncomp; c++) {
+    for (int c = 0; c < P.ncomp; c++, k++) {
       const int nb = P.bw[c] * P.bh[c];
-      const int k = L.foreign ? ifg++ : il++;
-      long long &t0 = L.foreign ? tf : tl;
-      mij::IlRec &j = d->h_trec[k];
+      const ScanGeom g = scan_geom(P, c);
+      mij::RecJob &j = d->h_trec[k];
       memset(&j, 0, sizeof j);
       j.off = L.off[c];
       j.nblocks = nb;
       j.bw = P.bw[c];
       j.tile0 = (int)t0;
-      j.hs = L.foreign ? P.hs[c] : 1;
-      j.vs = L.foreign ? P.vs[c] : 1;
-      j.mcus_x = L.foreign ? P.mcus_x : P.bw[c];
-      j.seg = L.foreign && P.ri ? (int)std::min<long long>((long long)P.ri * P.hs[c] * P.vs[c], nb) : nb;
+      j.hs = g.hs;
+      j.vs = g.vs;
+      j.mcus_x = g.mcus_x;
+      j.seg = g.seg;
       mij::TcDc &q = d->h_tdc[k];
-      q.pre = (L.foreign ? d->t_dcf : d->t_dcl) + L.off[c] / 64;
-      q.tile = d->t_tile + (L.foreign ? tiles_l : 0) + t0;
+      q.pre = d->t_dc + L.off[c] / 64;
+      q.tile = d->t_tile + t0;
       q.abs = d->t_abs + ab;
       q.nblocks = nb;
       q.seg = j.seg;
@@ -2599,7 +1943,7 @@ static int tc_run(mij_decoder *d, int restart_rows, const XfPlan *plans, bool xf
       q.pad = 0;
       t0 += (nb + mij::DC_TILE - 1) / mij::DC_TILE;
       mij::TcComp &C = F.c[c];
-      C.plane = (L.foreign ? d->f_coef : d->d_coef) + L.off[c];
+      C.plane = d->d_coef + L.off[c];
       C.abs = q.abs;
       C.hs = X.hs[c];
       C.vs = X.vs[c];
@@ -2649,7 +1993,7 @@ static int tc_run(mij_decoder *d, int restart_rows, const XfPlan *plans, bool xf
   if (xform)
     HIP_TRY(hipMemcpyAsync(d->x_frames, d->h_xframes.data(), n * sizeof(mij::XfFrame), hipMemcpyHostToDevice,
                            d->stream));
-  HIP_TRY(hipMemcpyAsync(d->t_rec, d->h_trec.data(), ncomp * sizeof(mij::IlRec), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->t_rec, d->h_trec.data(), ncomp * sizeof(mij::RecJob), hipMemcpyHostToDevice, d->stream));
   HIP_TRY(hipMemcpyAsync(d->t_dcjobs, d->h_tdc.data(), ncomp * sizeof(mij::TcDc), hipMemcpyHostToDevice, d->stream));
   HIP_TRY(hipMemcpyAsync(d->t_frames, d->h_tframes.data(), n * sizeof(mij::TcFrame), hipMemcpyHostToDevice,
                          d->stream));
@@ -2657,18 +2001,9 @@ static int tc_run(mij_decoder *d, int restart_rows, const XfPlan *plans, bool xf
   HIP_TRY(hipMemsetAsync(d->t_err, 0, sizeof(int) * n, d->stream));
   HIP_TRY(hipEventRecord(d->tc_ev[0], d->stream));
   // absolute DCs: the decoder's prefix sums over the source's scan order
-  if (ncl) {
-    hipLaunchKernelGGL(mij::k_il_dc, dim3((unsigned)tiles_l), dim3(mij::DC_T), 0, d->stream, d->t_rec, ncl, d->d_coef,
-                       d->t_dcl, d->t_tile);
-    hipLaunchKernelGGL(mij::k_dec_dcbase<mij::IlRec>, dim3((ncl + 63) / 64), dim3(64), 0, d->stream, d->t_rec, ncl,
-                       d->t_tile);
-  }
-  if (ncf) {
-    hipLaunchKernelGGL(mij::k_il_dc, dim3((unsigned)tiles_f), dim3(mij::DC_T), 0, d->stream, d->t_rec + ncl, ncf,
-                       d->f_coef, d->t_dcf, d->t_tile + tiles_l);
-    hipLaunchKernelGGL(mij::k_dec_dcbase<mij::IlRec>, dim3((ncf + 63) / 64), dim3(64), 0, d->stream, d->t_rec + ncl,
-                       ncf, d->t_tile + tiles_l);
-  }
+  hipLaunchKernelGGL(mij::k_dec_dc, dim3((unsigned)tiles), dim3(mij::DC_T), 0, d->stream, d->t_rec, ncomp, d->d_coef,
+                     d->t_dc, d->t_tile);
+  hipLaunchKernelGGL(mij::k_dec_dcbase, dim3((ncomp + 63) / 64), dim3(64), 0, d->stream, d->t_rec, ncomp, d->t_tile);
   HIP_TRY(hipGetLastError());
   HIP_TRY(mij::launch_tc_abs(d->t_dcjobs, ncomp, max_comp, d->stream));
   if (xform) HIP_TRY(mij::launch_xf_blocks(d->x_frames, n, max_nblk, d->stream));

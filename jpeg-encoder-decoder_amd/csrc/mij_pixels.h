@@ -157,45 +157,11 @@ MIJ_HD void chroma10(const uint8_t *row, int c0, int cl, int cr, int v[10]) {
   v[9] = row[cr];
 }
 
-// Output rows 2r and 2r+1, columns 16g .. 16g+15 of a w x h frame: chroma
-// row r with rows r-1 / r+1 and columns 8g-1 / 8g+8 clamped to the plane, so
-// nothing outside the frame's three planes is read.  Y: w*h samples, Cb and
-// Cr: (w/2)*(h/2); pix: rows 3*w bytes apart.  Each output row leaves as
-// three aligned 16-byte stores (3*w and 48*g are multiples of 16).
-MIJ_HD void colour_tile(const uint8_t *Y, const uint8_t *Cb, const uint8_t *Cr, int w, int h, int r, int g, int rgb,
-                        uint8_t *pix) {
-  const int cw = w >> 1, ch = h >> 1;
-  const int ru = r > 0 ? r - 1 : 0, rd = r + 1 < ch ? r + 1 : ch - 1;
-  const int c0 = 8 * g, cl = c0 > 0 ? c0 - 1 : 0, cr = c0 + 8 < cw ? c0 + 8 : cw - 1;
-  int mid[10], nb[10], cb[2][16], crv[2][16];
-  chroma10(Cb + (long long)r * cw, c0, cl, cr, mid);
-  chroma10(Cb + (long long)ru * cw, c0, cl, cr, nb);
-  upsample16(mid, nb, cb[0]);
-  chroma10(Cb + (long long)rd * cw, c0, cl, cr, nb);
-  upsample16(mid, nb, cb[1]);
-  chroma10(Cr + (long long)r * cw, c0, cl, cr, mid);
-  chroma10(Cr + (long long)ru * cw, c0, cl, cr, nb);
-  upsample16(mid, nb, crv[0]);
-  chroma10(Cr + (long long)rd * cw, c0, cl, cr, nb);
-  upsample16(mid, nb, crv[1]);
-  MIJ_UNROLL
-  for (int row = 0; row < 2; row++) {
-    const long long y = 2LL * r + row;
-    const W4 yv = load_as<W4>(Y + y * w + 16 * g);
-    const uint32_t yw[4] = {yv.x, yv.y, yv.z, yv.w};
-    uint32_t wd[12];
-    colour16(yw, cb[row], crv[row], rgb, wd);
-    uint8_t *dst = pix + y * 3 * w + 48 * g;
-    store_as(dst, W4{wd[0], wd[1], wd[2], wd[3]});
-    store_as(dst + 16, W4{wd[4], wd[5], wd[6], wd[7]});
-    store_as(dst + 32, W4{wd[8], wd[9], wd[10], wd[11]});
-  }
-}
-
 // ---------------------------------------------------------------------------
-// Every other layout the decoder accepts (DESIGN.md "Decoding ordinary
-// baseline files"): greyscale, 4:4:4, 4:2:2 and 4:2:0 at any size, on planes
-// padded to whole MCUs.  libjpeg's rules: the chroma edges are those of the
+// The colour stage for every layout the decoder accepts (DESIGN.md "Decoding
+// ordinary baseline files"): greyscale, 4:4:4, 4:2:2 and 4:2:0 at any size,
+// on planes padded to whole MCUs (the encoder's own frames, multiples of 16,
+// have no padding).  libjpeg's rules: the chroma edges are those of the
 // component's real size, ceil(w / 2) x ceil(h / 2) (downsampled_width /
 // _height), not of the padded plane; the "fancy" upsamplers only run when
 // that width is > 2, else each sample is replicated (jdsample.c).
@@ -304,9 +270,10 @@ MIJ_HD void colour_tile_any(const uint8_t *Y, const uint8_t *Cb, const uint8_t *
       crv[1][k] = crv[0][k];
     }
   }
-  for (int row = 0; row < nrows; row++) {
+  MIJ_UNROLL
+  for (int row = 0; row < 2; row++) {
     const long long y = (long long)nrows * u + row;
-    if (y >= G.h) break;
+    if (row >= nrows || y >= G.h) break;
     uint32_t yw[4], wd[12];
     row16(Y + y * G.yp, 16 * g, G.yp, yw);
     if (G.mode == PIX_GREY) {
@@ -464,6 +431,11 @@ MIJ_HD void scaled_geometry(int w, int h, int ncomp, const int *hs, const int *v
   else if (fx == 1 && fy == 1) G.mode = PIX_444;
   else if (fy == 1) G.mode = (G.c[1].cw > 2 && s > 1) ? PIX_H2V1 : PIX_H2V1_REP;  // libjpeg: no fancy upsampling at IDCT size 1
   else G.mode = (G.c[1].cw > 2 && s > 1) ? PIX_H2V2 : PIX_H2V2_REP;
+}
+
+// what colour_tile_any needs of it
+MIJ_HD PixGeom pix_geometry(const ScaledGeom &G) {
+  return PixGeom{G.ow, G.oh, G.mode, G.c[0].pitch, G.c[1].pitch, G.c[1].cw, G.c[1].ch, (3LL * G.ow + 15) / 16 * 16};
 }
 
 }  // namespace mij

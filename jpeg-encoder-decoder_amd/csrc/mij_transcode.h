@@ -10,7 +10,7 @@ constexpr int TC_CH = 4096;
 // bytes before the entropy data at most: APP0 20 + 3 DQT x 69 + 4 DHT x (21 + 256) + SOF0 19 + DRI 6 + SOS 14
 constexpr int TC_HDR_MAX = 1408;
 
-// One component's absolute DCs from the prefix sums k_il_dc / k_dec_dcbase
+// One component's absolute DCs from the prefix sums k_dec_dc / k_dec_dcbase
 // left (mij_decode.hip): with P(s) = pre[s] + tile[s / DC tile] over the
 // source's scan order, block s has P(s) - P(first block of its segment - 1).
 struct TcDc {
@@ -24,7 +24,7 @@ struct TcDc {
 };
 
 struct TcComp {
-  const int16_t *plane;  // padded plane in the arena or the legacy buffer: raster blocks of 64 zigzag coefficients
+  const int16_t *plane;  // padded plane in the arena: raster blocks of 64 zigzag coefficients
   const int16_t *abs;    // its absolute DCs (TcDc::abs)
   int hs, vs, bw;        // blocks per MCU across and down, blocks across the plane
   int pad;

@@ -4,7 +4,7 @@
 // optimised for it and restart intervals of whole MCU rows.  Nothing is
 // dequantised: the planes, their MCU padding included, are coded as decoded.
 //
-//   (k_il_dc / k_dec_dcbase, mij_decode.hip: prefix sums of the coded DC
+//   (k_dec_dc / k_dec_dcbase, mij_decode.hip: prefix sums of the coded DC
 //    differences over the source's scan order)
 //   k_tc_abs      one absolute DC per block
 //   k_tc_hist     symbol counts in the new scan's order (DC prediction per

@@ -1,6 +1,6 @@
 // foreign_pixels_check.cpp -- runs the decoder's pixel arithmetic for every
 // accepted layout (csrc/mij_pixels.h: idct_block and colour_tile_any, the code
-// k_il_idct and k_il_colour call) on the host, unit by unit as the kernels do,
+// k_dec_idct<8> and k_dec_colour call) on the host, unit by unit as the kernels do,
 // for tests/test_foreign_model.py to compare with the numpy model.
 // Input file: int32 w, h, ncomp, mode (PIX_*), then bw, bh and q[64] (zigzag
 // order) per component, then per component its padded int16 coefficient plane

@@ -28,7 +28,7 @@ int main(int argc, char **argv) {
   const size_t off[3] = {0, ny, ny + ny / 4};
   for (int c = 0; c < 3; c++) {
     const int bw = c ? w / 16 : w / 8, nblocks = (int)((c ? ny / 4 : ny) / 64);
-    uint32_t dc = 0;  // k_dec_dc: running sum modulo 2^32
+    uint32_t dc = 0;  // k_dec_dc on a one-component scan: running sum modulo 2^32 in raster order
     for (int b = 0; b < nblocks; b++) {
       const int16_t *blk = &coef[off[c] + 64 * (size_t)b];
       dc += (uint32_t)(int32_t)blk[0];
@@ -39,10 +39,15 @@ int main(int argc, char **argv) {
         mij::store_as(&planes[off[c] + ((size_t)8 * by + r) * 8 * bw + 8 * bx], mij::W2{rows[r][0], rows[r][1]});
     }
   }
+  // the frame's geometry as the decoder computes it: 4:2:0 at full size
+  const int hs[3] = {2, 1, 1}, vs[3] = {2, 1, 1}, bw[3] = {w / 8, w / 16, w / 16}, bh[3] = {h / 8, h / 16, h / 16};
+  mij::ScaledGeom S;
+  mij::scaled_geometry(w, h, 3, hs, vs, bw, bh, 1, S);
+  const mij::PixGeom G = mij::pix_geometry(S);
   for (int r = 0; r < h / 2; r++)
     for (int g = 0; g < w / 16; g++) {
-      mij::colour_tile(&planes[0], &planes[ny], &planes[ny + ny / 4], w, h, r, g, 1, rgb.data());
-      mij::colour_tile(&planes[0], &planes[ny], &planes[ny + ny / 4], w, h, r, g, 0, bgr.data());
+      mij::colour_tile_any(&planes[0], &planes[ny], &planes[ny + ny / 4], G, r, g, 1, rgb.data());
+      mij::colour_tile_any(&planes[0], &planes[ny], &planes[ny + ny / 4], G, r, g, 0, bgr.data());
     }
   f = fopen(argv[2], "wb");
   if (!f || fwrite(planes.data(), 1, ns, f) != ns || fwrite(rgb.data(), 1, 3 * ny, f) != 3 * ny ||

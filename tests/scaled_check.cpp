@@ -1,7 +1,7 @@
 // scaled_check.cpp -- runs the arithmetic of decoding at 1/2, 1/4, 1/8 scale
 // (csrc/mij_pixels.h: scaled_geometry, idct4_block, idct2_block, idct1_block,
-// idct_block and colour_tile_any on the scaled planes, the code k_sc_idct and
-// k_il_colour call) on the host, for tests/test_scaled_model.py to compare
+// idct_block and colour_tile_any on the scaled planes, the code k_dec_idct<S> and
+// k_dec_colour call) on the host, for tests/test_scaled_model.py to compare
 // with the numpy model.
 // Input file: int32 w, h, ncomp, denom, then hs, vs, bw, bh and q[64] (zigzag
 // order) per component, then per component its padded int16 coefficient plane

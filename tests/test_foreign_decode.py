@@ -8,9 +8,12 @@ import os
 import numpy as np
 import pytest
 
+import decode_cases as DC
 import foreign_cases as FC
 import mijpeg
+import oracle as O
 import recipes
+import scaled_model as SM
 
 pytestmark = pytest.mark.gpu
 
@@ -170,6 +173,88 @@ def test_repeated_decodes_are_identical():
             for i, n in enumerate(names):
                 assert (d.pixels(i) == FC.model(n).rgb).all(), n
         assert len(passes) == 1
+    finally:
+        d.close()
+
+
+def _legacy_48x32():
+    bgr = recipes.noise(32, 48, 21)
+    Y, Cb, Cr, _, jpg = O.cref_stages(bgr, 50)
+    return DC.Case("noise_48x32_q50", jpg, Y, Cb, Cr, 48, 32)
+
+
+def test_every_frame_in_one_arena():
+    """the encoder's three-scan streams and ordinary files share one set of
+    buffers: every frame's pixels begin where the previous frame's end, and a
+    three-scan frame reads the same there as in a decoder of its own"""
+    legacy = {0: DC.case("noise_16x16_q50"), 2: _legacy_48x32(), 4: DC.case("sample_64x64")}
+    foreign = {1: "420_35x21", 3: "grey_35x21"}
+    streams = [legacy[i].jpg if i in legacy else FC.jpg(foreign[i]) for i in range(5)]
+    size = lambda i: (legacy[i].w, legacy[i].h) if i in legacy else (FC.model(foreign[i]).w, FC.model(foreign[i]).h)
+    d = mijpeg.Decoder(64, 64, 5)
+    try:
+        d.decode(streams)
+        d.reconstruct("rgb")
+        end = None
+        for i in range(5):
+            w, h = size(i)
+            ptr, pitch = d.device_pixels(i)
+            assert pitch == (3 * w + 15) // 16 * 16
+            assert end is None or ptr == end, i
+            end = ptr + pitch * h
+        for i in range(5):
+            if i in foreign:
+                m = FC.model(foreign[i])
+                _check_frame(d, i, m)
+                _check_pixels(d, i, m, "rgb")
+                with pytest.raises(mijpeg.MijError, match="not of the encoder's layout.*mij_decoder_component"):
+                    d.coefs(i)
+                with pytest.raises(mijpeg.MijError, match="not of the encoder's layout.*mij_decoder_plane"):
+                    d.planes(i)
+                continue
+            c = legacy[i]
+            assert (d.pixels(i) == c.rgb).all(), i
+            alone = mijpeg.Decoder(c.w, c.h, 1)
+            try:
+                alone.decode([c.jpg])
+                alone.reconstruct("rgb")
+                for got, want, model in zip(d.coefs(i), alone.coefs(0), c.coefs):
+                    assert (got == want).all() and (got.ravel() == np.asarray(model).ravel()).all(), i
+                for got, want, model in zip(d.planes(i), alone.planes(0), c.planes):
+                    assert (got == want).all() and (got == model).all(), i
+                assert (d.pixels(i) == alone.pixels(0)).all(), i
+            finally:
+                alone.close()
+        d.reconstruct("rgb", scale=2)
+        for i in range(5):
+            if i in foreign:
+                s = SM.scaled(FC.model(foreign[i]), 2)
+            else:
+                c = legacy[i]
+                s = SM.scaled_legacy(*c.coefs, *c.dqt, c.w, c.h, 2)
+            got, want = d.pixels(i), s.pixels("rgb")
+            assert got.shape == want.shape and (got == want).all(), i
+    finally:
+        d.close()
+
+
+def test_corrupt_one_component_scan_in_a_mixed_call():
+    """the first of a three-scan stream's scans cut short, behind an ordinary
+    file in the same call: the call fails naming that stream, and the decoder
+    goes on working"""
+    with open(os.path.join(recipes.GOLDEN, "sample_64x64.jpg"), "rb") as f:
+        jpg = f.read()
+    bad = jpg[:330] + jpg[-2:]
+    good, m = FC.jpg("420_35x21"), FC.model("420_35x21")
+    d = mijpeg.Decoder(64, 64, 2)
+    try:
+        with pytest.raises(mijpeg.MijError, match="(?i)corrupt") as e:
+            d.decode([good, bad])
+        assert "stream 1" in str(e.value), str(e.value)
+        d.decode([good])
+        d.reconstruct("rgb")
+        _check_frame(d, 0, m)
+        assert (d.pixels(0) == m.rgb).all()
     finally:
         d.close()
 

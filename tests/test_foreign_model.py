@@ -82,7 +82,7 @@ def pixels_check(tmp_path_factory):
 
 @pytest.mark.parametrize("name", FC.SMALL)
 def test_kernel_arithmetic_on_the_host_equals_model(name, pixels_check, tmp_path):
-    """idct_block and colour_tile_any (what k_il_idct and k_il_colour call),
+    """idct_block and colour_tile_any (what k_dec_idct<8> and k_dec_colour call),
     compiled for the host and driven unit by unit as the kernels drive them"""
     m = FC.model(name)
     src, dst = tmp_path / "in.bin", tmp_path / "out.bin"

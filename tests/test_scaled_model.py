@@ -117,7 +117,7 @@ def scaled_check(tmp_path_factory):
 @pytest.mark.parametrize("name", FC.SMALL)
 def test_kernel_arithmetic_on_the_host_equals_model(name, scaled_check, tmp_path):
     """scaled_geometry, the block IDCTs of every size and colour_tile_any on
-    the scaled planes (what k_sc_idct and k_il_colour call), compiled for the host"""
+    the scaled planes (what k_dec_idct<S> and k_dec_colour call), compiled for the host"""
     m = FC.model(name)
     for denom in SC.DENOMS:
         s = SC.model(name, denom)
