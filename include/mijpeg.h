@@ -682,6 +682,59 @@ int mij_decoder_scaled_layout(mij_decoder *d, int frame, int denom, int *out, in
 int mij_decode_scaled(const uint8_t *jpg, size_t len, int order, int denom, uint8_t *out, size_t cap, int *w,
                       int *h);
 
+/* ---- resize: thumbnails at any size --------------------------
+ * What PIL.Image.resize(size, resample) gives for BOX, BILINEAR and BICUBIC
+ * (no `box`, no `reducing_gap`), byte for byte, on 3-byte interleaved 8-bit
+ * pixels in device memory: Pillow's fixed-point resampler (22-bit weights from
+ * double-precision coefficients, int32 sums, horizontal pass to an 8-bit
+ * intermediate, then vertical; a pass whose sizes are equal is skipped, both
+ * equal is a copy).  The channels are resampled alike, so the byte order does
+ * not matter.  Sizes are 1..65535 a side.
+ *
+ * A source image is any device pointer and pitch (>= 3 * w), no alignment
+ * asked, so it may be a rectangle inside a larger image (crop, then resize).
+ * It is read as mij_batch_pad_input reads: whole aligned 4-byte words that hold
+ * at least one byte of the image's rows.  Frames of a call may all differ in
+ * both sizes.  The results live in the resizer's buffers, which grow on
+ * demand: rows 3 * out_w rounded up to 16 bytes apart (the bytes past 3 *
+ * out_w hold anything), as mij_decoder_device_pixels lays them out, so they go
+ * to mij_batch_pad_input unchanged.
+ *
+ * MIJ_EINVAL before any device work, the message naming the frame and the
+ * argument: an unknown filter, a size outside 1..65535, a pitch under 3 * w,
+ * n outside 1..max_frames, a null image, a pixels call before a resize.  A
+ * refused call leaves the previous result served. */
+enum { MIJ_RS_BOX = 0, MIJ_RS_BILINEAR = 1, MIJ_RS_BICUBIC = 2 };
+typedef struct { const void *px; long long pitch; int w, h; } mij_image;   /* device memory */
+typedef struct mij_resizer mij_resizer;
+mij_resizer *mij_resizer_create(int device, int max_frames);
+void mij_resizer_destroy(mij_resizer *r);
+/* n device images to out_wh = {w0, h0, w1, h1, ...}; async on the resizer's stream */
+int mij_resizer_resize(mij_resizer *r, const mij_image *src, const int *out_wh, int n, int filter);
+/* device address of frame's pixels and their pitch; valid until the next
+ * resize, complete once the resizer's stream has reached this point */
+void *mij_resizer_device_pixels(mij_resizer *r, int frame, long long *pitch);
+/* host copy, rows pitch bytes apart (0 = 3 * out_w); MIJ_ENOSPC for a short cap; waits */
+int mij_resizer_pixels(mij_resizer *r, int frame, uint8_t *dst, size_t cap, long long pitch);
+int mij_resizer_ms(mij_resizer *r, float ms[2]);           /* {horizontal, vertical}; waits */
+void *mij_resizer_stream(mij_resizer *r);
+int mij_resizer_set_stream(mij_resizer *r, void *stream);  /* as mij_batch_set_stream */
+/* host to host; cap 0 asks for the size (MIJ_ENOSPC, before any device work) */
+int mij_resize(const uint8_t *px, int stride_px, int w, int h, int out_w, int out_h, int filter,
+               uint8_t *out, size_t cap);
+/* jpg -> jpg at exactly out_w x out_h: mij_decoder_reconstruct_scaled at
+ * mij_thumbnail_denom, a resize of the whole scaled image, then
+ * mij_batch_pad_input + mij_batch_encode_interleaved (4:2:0, no restart
+ * intervals: mij_encode_any's stream), all on one stream, the pixels never
+ * leaving the device.  Refuses what mij_decode refuses, with its message;
+ * MIJ_ENOSPC with mij_max_jpg_bytes_any(out_w, out_h, 0) in *out_len when cap
+ * is under it, before any device work */
+int mij_thumbnail(const uint8_t *jpg, size_t len, int out_w, int out_h, int filter, int quality,
+                  uint8_t *out, size_t cap, size_t *out_len);
+/* Pillow's Image.draft rule: the largest of 8, 4, 2, 1 that is <= min(w /
+ * out_w, h / out_h) in integer division, 1 if none is (and for sizes < 1) */
+int mij_thumbnail_denom(int w, int h, int out_w, int out_h);   /* host only */
+
 /* ---- lossless transcoding ------------------------------------
  * What jpegtran -optimize does, on the GPU: every frame of the last decode,
  * of either kind above, becomes one standard interleaved baseline stream

@@ -7,6 +7,7 @@ GPU is visible, every call raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -55,6 +56,9 @@ EXPORTS = [
     "mij_decoder_reconstruct_scaled", "mij_decoder_scaled_layout", "mij_decode_scaled",
     "mij_max_jpg_bytes_sampled", "mij_batch_encode_sampled", "mij_batch_sampled_component",
     "mij_batch_sampled_layout", "mij_encode_sampled",
+    "mij_resizer_create", "mij_resizer_destroy", "mij_resizer_resize", "mij_resizer_device_pixels", "mij_resizer_pixels",
+    "mij_resizer_ms", "mij_resizer_stream", "mij_resizer_set_stream", "mij_resize", "mij_thumbnail",
+    "mij_thumbnail_denom",
 ]
 
 
@@ -263,6 +267,21 @@ def load() -> C.CDLL:
         lib.mij_batch_sampled_component.argtypes = [p, i, i, p, sz]
         lib.mij_batch_sampled_layout.argtypes = [p, i, p, i]
         lib.mij_encode_sampled.argtypes = [p, i, i, i, i, i, i, i, p, sz, C.POINTER(sz)]
+        lib.mij_resizer_create.restype = p
+        lib.mij_resizer_create.argtypes = [i, i]
+        lib.mij_resizer_destroy.restype = None
+        lib.mij_resizer_destroy.argtypes = [p]
+        lib.mij_resizer_resize.argtypes = [p, p, p, i, i]
+        lib.mij_resizer_device_pixels.restype = p
+        lib.mij_resizer_device_pixels.argtypes = [p, i, C.POINTER(C.c_longlong)]
+        lib.mij_resizer_pixels.argtypes = [p, i, p, sz, C.c_longlong]
+        lib.mij_resizer_ms.argtypes = [p, p]
+        lib.mij_resizer_stream.restype = p
+        lib.mij_resizer_stream.argtypes = [p]
+        lib.mij_resizer_set_stream.argtypes = [p, p]
+        lib.mij_resize.argtypes = [p, i, i, i, i, i, i, p, sz]
+        lib.mij_thumbnail.argtypes = [p, sz, i, i, i, i, p, sz, C.POINTER(sz)]
+        lib.mij_thumbnail_denom.argtypes = [i, i, i, i]
     except AttributeError:
         if not os.environ.get("MIJ_LIB"):  # older builds only in A/B timing runs
             raise
@@ -1275,3 +1294,139 @@ class Decoder:
         ms = C.c_float(0)
         _check(self.lib.mij_decoder_transcode_ms(self.h_, C.byref(ms)), "decoder_transcode_ms")
         return float(ms.value)
+
+
+# ---- resize: thumbnails at any size ---------------------------
+RS_FILTERS = {"box": 0, "bilinear": 1, "bicubic": 2}  # MIJ_RS_*
+
+
+class Image(C.Structure):
+    """mij_image: 3-byte pixels in device memory, rows pitch bytes apart"""
+    _fields_ = [("px", C.c_void_p), ("pitch", C.c_longlong), ("w", C.c_int), ("h", C.c_int)]
+
+
+def _filter(name) -> int:
+    if isinstance(name, str):
+        if name not in RS_FILTERS:
+            raise MijError(f"filter {name!r}: one of {', '.join(RS_FILTERS)}")
+        return RS_FILTERS[name]
+    return int(name)
+
+
+def thumbnail_denom(w: int, h: int, out_w: int, out_h: int) -> int:
+    """mij_thumbnail_denom: the scale 1/denom Pillow's Image.draft picks for a
+    w x h file asked for out_w x out_h; host only"""
+    return int(load().mij_thumbnail_denom(w, h, out_w, out_h))
+
+
+def fit_size(w: int, h: int, max_w: int, max_h: int):
+    """the size Image.thumbnail((max_w, max_h)) gives a w x h image: inside the
+    box, the aspect ratio kept as nearly as whole pixels allow, never larger
+    than the image; host only"""
+    def round_aspect(number, key):
+        return max(min(math.floor(number), math.ceil(number), key=key), 1)
+    x, y = int(max_w), int(max_h)
+    if x < 1 or y < 1 or w < 1 or h < 1:
+        raise MijError(f"fit_size: {w}x{h} into {max_w}x{max_h}")
+    if x >= w and y >= h:
+        return w, h
+    aspect = w / h
+    if x / y >= aspect:
+        x = round_aspect(y * aspect, key=lambda n: abs(aspect - n / y))
+    else:
+        y = round_aspect(x / aspect, key=lambda n: 0 if n == 0 else abs(aspect - x / n))
+    return x, y
+
+
+def resize(frame: np.ndarray, size, filter="bicubic") -> np.ndarray:
+    """mij_resize: (h, w, 3) uint8 pixels -> (size[1], size[0], 3), byte for
+    byte PIL.Image.resize(size, FILTER) for box, bilinear and bicubic; host to
+    host through the GPU"""
+    lib = load()
+    if frame.ndim != 3 or frame.shape[2] != 3 or frame.dtype != np.uint8:
+        raise MijError("resize: an (h, w, 3) uint8 array")
+    frame = np.ascontiguousarray(frame)
+    h, w = frame.shape[:2]
+    ow, oh = int(size[0]), int(size[1])
+    out = np.zeros((max(oh, 0), max(ow, 0), 3), np.uint8)
+    _check(lib.mij_resize(_ptr(frame), w, w, h, ow, oh, _filter(filter), _ptr(out), out.nbytes), "mij_resize")
+    return out
+
+
+def thumbnail(jpg: bytes, size, filter="bicubic", quality: int = 75) -> bytes:
+    """mij_thumbnail: one baseline stream -> a JPEG of exactly size = (w, h):
+    decoded at thumbnail_denom, resized, encoded as encode_any encodes; the
+    pixels never leave the device"""
+    lib = load()
+    buf = np.frombuffer(jpg, np.uint8)
+    ow, oh = int(size[0]), int(size[1])
+    n = C.c_size_t(0)
+    out = np.zeros(max(int(lib.mij_max_jpg_bytes_any(ow, oh, 0)), 1), np.uint8)
+    _check(lib.mij_thumbnail(_ptr(buf), buf.size, ow, oh, _filter(filter), int(quality), _ptr(out), out.nbytes,
+                             C.byref(n)), "mij_thumbnail")
+    return out[:n.value].tobytes()
+
+
+class Resizer:
+    """Device images of any size, pointer and pitch -> resampled device images
+    (mij_resizer_*): Pillow's Image.resize for box, bilinear and bicubic, byte
+    for byte, frames of a call in one launch per pass."""
+
+    def __init__(self, max_frames: int, device: int = 0):
+        self.lib = load()
+        self.sizes_ = []
+        self.h_ = self.lib.mij_resizer_create(device, max_frames)
+        if not self.h_:
+            raise MijError("mij_resizer_create failed: "
+                           f"{self.lib.mij_strerror(self.lib.mij_last_error()).decode()}: "
+                           f"{self.lib.mij_last_message().decode(errors='replace')}")
+
+    def close(self) -> None:
+        if self.h_:
+            self.lib.mij_resizer_destroy(self.h_)
+            self.h_ = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def resize(self, images, sizes, filter="bicubic") -> None:
+        """images: (device address, pitch, w, h) each; sizes: (out_w, out_h)
+        each; asynchronous on the resizer's stream"""
+        n = len(images)
+        src = (Image * max(n, 1))(*[Image(int(a), int(pitch), int(w), int(h)) for a, pitch, w, h in images])
+        wh = (C.c_int * (2 * max(n, 1)))(*[int(v) for s in sizes for v in s])
+        _check(self.lib.mij_resizer_resize(self.h_, src, wh, n, _filter(filter)), "resizer_resize")
+        self.sizes_ = [(int(s[0]), int(s[1])) for s in sizes]
+
+    def pixels(self, frame: int) -> np.ndarray:
+        """(out_h, out_w, 3) uint8 pixels of `frame` of the last resize; waits"""
+        w, h = self.sizes_[frame] if 0 <= frame < len(self.sizes_) else (1, 1)
+        out = np.zeros((h, w, 3), np.uint8)
+        _check(self.lib.mij_resizer_pixels(self.h_, frame, _ptr(out), out.nbytes, 0), "resizer_pixels")
+        return out
+
+    def device_pixels(self, frame: int):
+        """(device address, pitch in bytes) of `frame`'s pixels: valid until
+        the next resize, complete once the resizer's stream has run it;
+        Batch.pad_input takes them as they are"""
+        pitch = C.c_longlong(0)
+        ptr = self.lib.mij_resizer_device_pixels(self.h_, frame, C.byref(pitch))
+        if not ptr:
+            _check(self.lib.mij_last_error() or 1, "resizer_device_pixels")
+        return int(ptr), int(pitch.value)
+
+    def ms(self):
+        """(horizontal, vertical) HIP-event milliseconds of the last resize; waits for it"""
+        ms = (C.c_float * 2)()
+        _check(self.lib.mij_resizer_ms(self.h_, ms), "resizer_ms")
+        return float(ms[0]), float(ms[1])
+
+    def stream_ptr(self) -> int:
+        return int(self.lib.mij_resizer_stream(self.h_) or 0)
+
+    def set_stream(self, stream) -> None:
+        """run on the caller's hipStream_t (0 / None: the resizer's own), as Batch.set_stream"""
+        _check(self.lib.mij_resizer_set_stream(self.h_, stream or None), "resizer_set_stream")
