@@ -336,8 +336,9 @@ size_t mij_max_jpg_bytes_sampled(int w, int h, int sampling, int restart_rows);
  * buffers, which grow with later calls, and grows the per-frame output
  * capacity to mij_max_jpg_bytes_sampled of the canvas. */
 int mij_batch_encode_sampled(mij_batch *b, int nframes, int sampling, int restart_rows);
-/* The planes the last mij_batch_encode_sampled coded, as mij_decoder_layout
- * and mij_decoder_component show a decoded stream's: layout = {w, h, ncomp,
+/* The planes the last mij_batch_encode_sampled (or mij_batch_encode_libjpeg,
+ * below) coded, as mij_decoder_layout and mij_decoder_component show a
+ * decoded stream's: layout = {w, h, ncomp,
  * hmax, vmax, mcus_x, mcus_y, Ri, 1} then {h, v, tq, blocks across, blocks
  * down} per component (MIJ_ENOSPC under 9 + 5 * ncomp ints); a component =
  * its padded plane, raster blocks of 64 zigzag coefficients, DC absolute. */
@@ -347,6 +348,38 @@ int mij_batch_sampled_component(mij_batch *b, int frame, int comp, int16_t *dst,
  * mij_max_jpg_bytes_sampled(w, h, sampling, restart_rows) in *out_len when
  * cap is under it, come before any device work. */
 int mij_encode_sampled(const uint8_t *px, int stride_px, int w, int h, int order, int quality,
+                       int sampling, int restart_rows, uint8_t *out, size_t cap, size_t *out_len);
+
+/* ---- encoding as libjpeg does --------------------------------
+ * The same streams with libjpeg's arithmetic in front of the entropy coder,
+ * so that the DQTs and every quantised coefficient are those of the file
+ * libjpeg (cjpeg, Pillow's save(quality, subsampling), ImageMagick) writes for
+ * the same pixels, quality and sampling: the Annex K tables on the IJG scale
+ * (s = 5000 / Q under 50, else 200 - 2 Q; (base s + 50) / 100 in 1..255);
+ * fixed-point colour conversion; chroma downsampled without smoothing, (a + b
+ * + bias) >> 1 with bias 0, 1, ... at 4:2:2 and (a + b + c + d + bias) >> 2
+ * with bias 1, 2, ... at 4:2:0; pixels replicated to the right, and downward
+ * to a whole row group, the component's last sample row below that; the
+ * blocks of the MCU padding that hold no sample with no AC and the DC of the
+ * block before them in the MCU; the "islow" integer DCT; a quantiser that
+ * rounds the magnitude.  Huffman tables and headers are this library's own:
+ * the files are not byte-equal to libjpeg's, their decoded pixels are.
+ *
+ * mij_libjpeg_tables: the luma then the chroma table of a quality, 64 bytes
+ * each in zigzag order as mij_decoder_info reports a stream's; MIJ_EINVAL
+ * outside 1..100.  Host only. */
+int mij_libjpeg_tables(int quality, uint8_t dqt[128]);
+/* mij_batch_encode_sampled with that arithmetic, the batch's quality read on
+ * the IJG scale, at all four MIJ_SAMP_* (4:2:0 too goes through this path,
+ * not through mij_batch_encode_interleaved): the same preconditions,
+ * refusals, mid-call wait, buffer growth and result calls.  Afterwards
+ * mij_batch_sampled_layout / _component serve its planes: they follow the
+ * last mij_batch_encode_sampled or mij_batch_encode_libjpeg. */
+int mij_batch_encode_libjpeg(mij_batch *b, int nframes, int sampling, int restart_rows);
+/* mij_encode_sampled with that arithmetic.  Every MIJ_EINVAL, and MIJ_ENOSPC
+ * with mij_max_jpg_bytes_sampled(w, h, sampling, restart_rows) in *out_len
+ * when cap is under it, come before any device work. */
+int mij_encode_libjpeg(const uint8_t *px, int stride_px, int w, int h, int order, int quality,
                        int sampling, int restart_rows, uint8_t *out, size_t cap, size_t *out_len);
 
 /* ---- PPM ingest -----------------------------------
@@ -731,6 +764,12 @@ int mij_resize(const uint8_t *px, int stride_px, int w, int h, int out_w, int ou
  * is under it, before any device work */
 int mij_thumbnail(const uint8_t *jpg, size_t len, int out_w, int out_h, int filter, int quality,
                   uint8_t *out, size_t cap, size_t *out_len);
+/* mij_thumbnail with mij_batch_encode_libjpeg at `sampling` (MIJ_SAMP_*) at
+ * the end: the coefficients of Image.draft -> resize -> save(quality,
+ * subsampling).  The same refusals; the bound is mij_max_jpg_bytes_sampled(
+ * out_w, out_h, sampling, 0) */
+int mij_thumbnail_libjpeg(const uint8_t *jpg, size_t len, int out_w, int out_h, int filter, int quality,
+                          int sampling, uint8_t *out, size_t cap, size_t *out_len);
 /* Pillow's Image.draft rule: the largest of 8, 4, 2, 1 that is <= min(w /
  * out_w, h / out_h) in integer division, 1 if none is (and for sizes < 1) */
 int mij_thumbnail_denom(int w, int h, int out_w, int out_h);   /* host only */

@@ -15,6 +15,7 @@
 #include "mij_internal.h"
 #include "mij_interleave.h"
 #include "mij_sampled.h"
+#include "mij_ijg.h"
 #include "mij_transcode.h"
 #include "mijpeg.h"
 #include "mij_testing.h"
@@ -407,10 +408,13 @@ struct mij_batch {
     size_t bytes = 0;
   };
   enum { SB_PLANE, SB_ABS, SB_FR, SB_TFR, SB_TOUT, SB_BLK_BITS, SB_MCU_OFF, SB_ROW_BITS, SB_ROW_PRE, SB_IVAL,
-         SB_ROW_OFF, SB_BITS, SB_HDR, SB_RAW, SB_FFC, SB_COUNT };
+         SB_ROW_OFF, SB_BITS, SB_HDR, SB_RAW, SB_FFC, SB_IJGQ, SB_COUNT };
   DevBuf sb[SB_COUNT];
-  int samp_last = -1;  // sampling of the last mij_batch_encode_sampled (-1: none)
+  int samp_last = -1;  // sampling of the last mij_batch_encode_sampled / _libjpeg (-1: none)
   int samp_n = 0, samp_rr = 0;   // its frames and restart_rows
+  bool samp_ijg = false;         // it was mij_batch_encode_libjpeg
+  std::vector<IjgFrame> h_ifr;
+  IjgQuant h_ijgq;
   std::vector<int2> samp_wh;     // its frames' true sizes
   std::vector<SampFrame> h_sfr;
   std::vector<TcFrame> h_stf;
@@ -2565,26 +2569,28 @@ static T *samp_buf(mij_batch *b, int which) {
 
 // Waits for the device twice: before the descriptors are rebuilt (the last
 // call's uploads read them) and for the frames' bits, which size the scan
-// words; the write and the lengths stay asynchronous.
-extern "C" int mij_batch_encode_sampled(mij_batch *b, int nframes, int sampling, int restart_rows) {
-  if (pipe_check(b, "encode_sampled")) return g_err;
-  if (!samp_known(sampling)) return fail(MIJ_EINVAL, "encode_sampled: sampling %d (MIJ_SAMP_420 .. MIJ_SAMP_GRAY)", sampling);
-  if (nframes < 1 || nframes > b->cap) return fail(MIJ_EINVAL, "encode_sampled: bad frame count %d", nframes);
-  if (restart_rows < 0) return fail(MIJ_EINVAL, "encode_sampled: restart_rows %d", restart_rows);
+// words; the write and the lengths stay asynchronous.  ijg: libjpeg's
+// arithmetic and tables through k_ijg_fdct, 4:2:0 included,
+// in place of the reference's through k_samp_dct (and K1 at 4:2:0).
+static int samp_encode(mij_batch *b, int nframes, int sampling, int restart_rows, bool ijg, const char *what) {
+  if (pipe_check(b, what)) return g_err;
+  if (!samp_known(sampling)) return fail(MIJ_EINVAL, "%s: sampling %d (MIJ_SAMP_420 .. MIJ_SAMP_GRAY)", what, sampling);
+  if (nframes < 1 || nframes > b->cap) return fail(MIJ_EINVAL, "%s: bad frame count %d", what, nframes);
+  if (restart_rows < 0) return fail(MIJ_EINVAL, "%s: restart_rows %d", what, restart_rows);
   long long markers = 0;
   for (int i = 0; i < nframes; i++) {
     if (i >= (int)b->il_slot.size() || b->il_slot[i].x == 0)
-      return fail(MIJ_EINVAL, "encode_sampled: slot %d holds no padded input (pad_input / upload_any first)", i);
+      return fail(MIJ_EINVAL, "%s: slot %d holds no padded input (pad_input / upload_any first)", what, i);
     const int4 s = b->il_slot[i];
-    if (s.z != (b->rgb ? 1 : 0)) return fail(MIJ_EINVAL, "encode_sampled: set_rgb changed after slot %d was padded", i);
+    if (s.z != (b->rgb ? 1 : 0)) return fail(MIJ_EINVAL, "%s: set_rgb changed after slot %d was padded", what, i);
     const long long mk = samp_markers(s.x, s.y, sampling, restart_rows);
     if (mk < 0)
-      return fail(MIJ_EINVAL, "encode_sampled: restart interval of %d rows x %d MCUs is over 65535 MCUs (slot %d)",
+      return fail(MIJ_EINVAL, "%s: restart interval of %d rows x %d MCUs is over 65535 MCUs (slot %d)", what,
                   restart_rows, samp_grid(s.x, s.y, sampling).mcus_x, i);
     markers = std::max(markers, mk);
   }
   b->samp_last = -1;
-  if (sampling == MIJ_SAMP_420) {
+  if (sampling == MIJ_SAMP_420 && !ijg) {
     if (mij_batch_encode_interleaved(b, nframes, restart_rows)) return g_err;
   } else {
     HIP_TRY(hipSetDevice(b->dev));
@@ -2601,12 +2607,13 @@ extern "C" int mij_batch_encode_sampled(mij_batch *b, int nframes, int sampling,
       max_nblk = (int)std::max<long long>(max_nblk, S.nblk);
       max_rows = std::max(max_rows, S.mcus_y);
     }
-    if (nblk > 0x7fff0000LL) return fail(MIJ_EINVAL, "encode_sampled: too many blocks");
+    if (nblk > 0x7fff0000LL) return fail(MIJ_EINVAL, "%s: too many blocks", what);
 #define SB_GROW(which, T, cnt) \
   if (samp_grow(b, mij_batch::which, sizeof(T) * (size_t)(cnt))) return g_err
     SB_GROW(SB_PLANE, int16_t, nblk * 64);
     SB_GROW(SB_ABS, int16_t, nblk);
-    SB_GROW(SB_FR, SampFrame, n);
+    SB_GROW(SB_FR, IjgFrame, n);  // (holds a SampFrame)
+    if (ijg) SB_GROW(SB_IJGQ, IjgQuant, 1);
     SB_GROW(SB_TFR, TcFrame, n);
     SB_GROW(SB_TOUT, TcOut, n);
     SB_GROW(SB_BLK_BITS, uint16_t, nblk);
@@ -2632,8 +2639,12 @@ extern "C" int mij_batch_encode_sampled(mij_batch *b, int nframes, int sampling,
     }
     // descriptors: the front end's and the coder's views of the same planes
     int q[2][64];
-    quality_tables(b->quality, q[0], q[1]);
+    if (ijg)
+      ijg_tables(b->quality, q[0], q[1]);
+    else
+      quality_tables(b->quality, q[0], q[1]);
     b->h_sfr.assign(n, SampFrame());
+    b->h_ifr.assign(ijg ? n : 0, IjgFrame());
     b->h_stf.assign(n, TcFrame());
     long long pb = 0, b0 = 0, m0 = 0, r0 = 0;
     for (int f = 0; f < n; f++) {
@@ -2686,27 +2697,55 @@ extern "C" int mij_batch_encode_sampled(mij_batch *b, int nframes, int sampling,
       b0 += F.nblk;
       m0 += (long long)S.mcus_x * S.mcus_y;
       r0 += S.mcus_y;
+      if (ijg) {
+        IjgFrame &I = b->h_ifr[f];
+        memset(&I, 0, sizeof I);
+        I.s = Q;
+        I.w = w;
+        I.h = h;
+        for (int c = 0; c < S.ncomp; c++) ijg_real_blocks(w, h, S, c, I.rbw[c], I.rbh[c]);
+      }
     }
     next_slot(b);
-    SampFrame *d_fr = samp_buf<SampFrame>(b, mij_batch::SB_FR);
+    void *d_fr = samp_buf<void>(b, mij_batch::SB_FR);
     TcFrame *d_tf = samp_buf<TcFrame>(b, mij_batch::SB_TFR);
     TcOut *d_to = samp_buf<TcOut>(b, mij_batch::SB_TOUT);
-    HIP_TRY(hipMemcpyAsync(d_fr, b->h_sfr.data(), n * sizeof(SampFrame), hipMemcpyHostToDevice, b->stream));
+    if (ijg) {
+      for (int c = 0; c < 2; c++)
+        for (int i = 0; i < 64; i++) b->h_ijgq.q[c][i] = ijg_qmagic(q[c][i]);
+      HIP_TRY(hipMemcpyAsync(d_fr, b->h_ifr.data(), n * sizeof(IjgFrame), hipMemcpyHostToDevice, b->stream));
+      HIP_TRY(hipMemcpyAsync(samp_buf<IjgQuant>(b, mij_batch::SB_IJGQ), &b->h_ijgq, sizeof(IjgQuant), hipMemcpyHostToDevice,
+                             b->stream));
+    } else {
+      HIP_TRY(hipMemcpyAsync(d_fr, b->h_sfr.data(), n * sizeof(SampFrame), hipMemcpyHostToDevice, b->stream));
+    }
     HIP_TRY(hipMemcpyAsync(d_tf, b->h_stf.data(), n * sizeof(TcFrame), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(hipMemsetAsync(b->d_hist, 0, sizeof(uint32_t) * n * 4 * 257, b->stream));
     HIP_TRY(hipMemsetAsync(b->d_err, 0, sizeof(int) * n, b->stream));
     b->hist_zero_n = b->band_hist_zero = 0;
     b->k1_err_zero = 0;
     if (b->timing) HIP_TRY(hipEventRecord(b->ev[0], b->stream));
-    SampArgs sa;
-    memset(&sa, 0, sizeof sa);
-    sa.in = b->d_in;
-    sa.in_fs = b->in_fs;
-    sa.pitch = b->pitch;
-    sa.sampling = sampling;
-    sa.fr = d_fr;
-    sa.tab = b->d_tab;
-    HIP_TRY(launch_samp_dct(sa, n, max_tiles, b->stream));
+    if (ijg) {
+      IjgArgs ia;
+      memset(&ia, 0, sizeof ia);
+      ia.in = b->d_in;
+      ia.in_fs = b->in_fs;
+      ia.pitch = b->pitch;
+      ia.sampling = sampling;
+      ia.fr = (const IjgFrame *)d_fr;
+      ia.qt = samp_buf<IjgQuant>(b, mij_batch::SB_IJGQ);
+      HIP_TRY(launch_ijg_fdct(ia, n, max_tiles, b->stream));
+    } else {
+      SampArgs sa;
+      memset(&sa, 0, sizeof sa);
+      sa.in = b->d_in;
+      sa.in_fs = b->in_fs;
+      sa.pitch = b->pitch;
+      sa.sampling = sampling;
+      sa.fr = (const SampFrame *)d_fr;
+      sa.tab = b->d_tab;
+      HIP_TRY(launch_samp_dct(sa, n, max_tiles, b->stream));
+    }
     if (b->timing)
       for (int e = 1; e <= 3; e++) HIP_TRY(hipEventRecord(b->ev[e], b->stream));
     TcArgs a;
@@ -2781,6 +2820,26 @@ extern "C" int mij_batch_encode_sampled(mij_batch *b, int nframes, int sampling,
   b->samp_last = sampling;
   b->samp_n = nframes;
   b->samp_rr = restart_rows;
+  b->samp_ijg = ijg;
+  return MIJ_OK;
+}
+
+extern "C" int mij_batch_encode_sampled(mij_batch *b, int nframes, int sampling, int restart_rows) {
+  return samp_encode(b, nframes, sampling, restart_rows, false, "encode_sampled");
+}
+
+extern "C" int mij_batch_encode_libjpeg(mij_batch *b, int nframes, int sampling, int restart_rows) {
+  return samp_encode(b, nframes, sampling, restart_rows, true, "encode_libjpeg");
+}
+
+extern "C" int mij_libjpeg_tables(int quality, uint8_t dqt[128]) {
+  g_err = MIJ_OK;
+  if (quality < 1 || quality > 100) return fail(MIJ_EINVAL, "mij_libjpeg_tables: quality %d (1..100)", quality);
+  if (!dqt) return fail(MIJ_EINVAL, "mij_libjpeg_tables: dqt is NULL");
+  int q[2][64];
+  ijg_tables(quality, q[0], q[1]);
+  for (int t = 0; t < 2; t++)
+    for (int z = 0; z < 64; z++) dqt[64 * t + z] = (uint8_t)q[t][k_zz[z]];
   return MIJ_OK;
 }
 
@@ -2816,7 +2875,7 @@ extern "C" int mij_batch_sampled_component(mij_batch *b, int frame, int comp, in
   const long long nb = (long long)S.bw[comp] * S.bh[comp];
   if (cap < (size_t)(64 * nb)) return fail(MIJ_ENOSPC, "sampled_component: need %lld coefficients", 64 * nb);
   const int16_t *src;
-  if (b->samp_last == MIJ_SAMP_420) {  // K1's planes of the padded frame: Y, Cb, Cr one after another
+  if (b->samp_last == MIJ_SAMP_420 && !b->samp_ijg) {  // K1's planes of the padded frame: Y, Cb, Cr one after another
     long long off = 0;
     for (int c = 0; c < comp; c++) off += (long long)S.bw[c] * S.bh[c];
     src = b->d_coef + (long long)frame * b->g.coef_fs + 64 * off;
@@ -2861,6 +2920,43 @@ extern "C" int mij_encode_sampled(const uint8_t *px, int stride_px, int w, int h
   b->rgb = order == MIJ_PIX_RGB;
   if (mij_batch_upload_any(b, px, stride_px, w, h, 0)) return g_err;
   if (mij_batch_encode_sampled(b, 1, sampling, restart_rows)) return g_err;
+  size_t n = 0;
+  if (mij_batch_output(b, 0, out, cap, &n)) return g_err;
+  if (out_len) *out_len = n;
+  return MIJ_OK;
+}
+
+// mij_encode_sampled's mirror with libjpeg's arithmetic, 4:2:0 included
+extern "C" int mij_encode_libjpeg(const uint8_t *px, int stride_px, int w, int h, int order, int quality,
+                                  int sampling, int restart_rows, uint8_t *out, size_t cap, size_t *out_len) {
+  std::lock_guard<std::mutex> l(g_mu);
+  g_err = MIJ_OK;
+  if (!samp_known(sampling)) return fail(MIJ_EINVAL, "mij_encode_libjpeg: sampling %d (MIJ_SAMP_420 .. MIJ_SAMP_GRAY)", sampling);
+  if (w < 1 || h < 1 || w > 65535 || h > 65535)
+    return fail(MIJ_EINVAL, "mij_encode_libjpeg: frame %dx%d (1..65535 each)", w, h);
+  if (quality < 1 || quality > 100 || (order != MIJ_PIX_BGR && order != MIJ_PIX_RGB) || restart_rows < 0)
+    return fail(MIJ_EINVAL, "mij_encode_libjpeg: quality %d, order %d or restart_rows %d out of range", quality, order,
+                restart_rows);
+  if (samp_markers(w, h, sampling, restart_rows) < 0)
+    return fail(MIJ_EINVAL, "mij_encode_libjpeg: restart interval of %d rows x %d MCUs is over 65535 MCUs", restart_rows,
+                samp_grid(w, h, sampling).mcus_x);
+  const size_t bound = mij_max_jpg_bytes_sampled(w, h, sampling, restart_rows);
+  if (out_len) *out_len = bound;
+  if (cap < bound) return fail(MIJ_ENOSPC, "mij_encode_libjpeg: need %zu bytes for %dx%d", bound, w, h);
+  if (!px || !out || stride_px < w)
+    return fail(MIJ_EINVAL, "mij_encode_libjpeg: null buffer or stride %d under the width", stride_px);
+  const int W = il_round16(w), H = il_round16(h);
+  if (!g_actx || g_actx->g.w < W || g_actx->g.h < H || g_actx->quality != quality) {
+    const int cw = g_actx && g_actx->g.w > W ? g_actx->g.w : W;
+    const int ch = g_actx && g_actx->g.h > H ? g_actx->g.h : H;
+    batch_free(g_actx);
+    g_actx = mij_batch_create(drop_device(), cw, ch, 1, quality);
+    if (!g_actx) return g_err;
+  }
+  mij_batch *b = g_actx;
+  b->rgb = order == MIJ_PIX_RGB;
+  if (mij_batch_upload_any(b, px, stride_px, w, h, 0)) return g_err;
+  if (mij_batch_encode_libjpeg(b, 1, sampling, restart_rows)) return g_err;
   size_t n = 0;
   if (mij_batch_output(b, 0, out, cap, &n)) return g_err;
   if (out_len) *out_len = n;

@@ -579,24 +579,27 @@ extern "C" int mij_thumbnail_denom(int w, int h, int out_w, int out_h) {
   return 1;
 }
 
-extern "C" int mij_thumbnail(const uint8_t *jpg, size_t len, int out_w, int out_h, int filter, int quality,
-                             uint8_t *out, size_t cap, size_t *out_len) {
+// sampling < 0: the reference's arithmetic at 4:2:0 (mij_thumbnail); otherwise
+// libjpeg's at that MIJ_SAMP_* (mij_thumbnail_libjpeg)
+static int thumbnail(const char *what, const uint8_t *jpg, size_t len, int out_w, int out_h, int filter, int quality,
+                     int sampling, uint8_t *out, size_t cap, size_t *out_len) {
   mij_clear_error();
   if (out_len) *out_len = 0;
-  if (rs_check_filter("mij_thumbnail", filter)) return MIJ_EINVAL;
+  if (rs_check_filter(what, filter)) return MIJ_EINVAL;
   if (!rs_side(out_w) || !rs_side(out_h))
-    return mij_fail(MIJ_EINVAL, "mij_thumbnail: out size %dx%d (1..65535 each)", out_w, out_h);
-  if (quality < 1 || quality > 100) return mij_fail(MIJ_EINVAL, "mij_thumbnail: quality %d (1..100)", quality);
-  if (!jpg) return mij_fail(MIJ_EINVAL, "mij_thumbnail: jpg is NULL");
+    return mij_fail(MIJ_EINVAL, "%s: out size %dx%d (1..65535 each)", what, out_w, out_h);
+  if (quality < 1 || quality > 100) return mij_fail(MIJ_EINVAL, "%s: quality %d (1..100)", what, quality);
+  if (sampling > MIJ_SAMP_GRAY) return mij_fail(MIJ_EINVAL, "%s: sampling %d (MIJ_SAMP_420 .. MIJ_SAMP_GRAY)", what, sampling);
+  if (!jpg) return mij_fail(MIJ_EINVAL, "%s: jpg is NULL", what);
   // the headers, through mij_decode asked for the size: what it refuses is refused here, with its message
   int w = 0, h = 0;
   uint8_t probe;
   if (int rc = mij_decode(jpg, len, MIJ_PIX_BGR, &probe, 0, &w, &h); rc != MIJ_ENOSPC) return rc;
   mij_clear_error();
-  const size_t bound = mij_max_jpg_bytes_any(out_w, out_h, 0);
+  const size_t bound = sampling < 0 ? mij_max_jpg_bytes_any(out_w, out_h, 0) : mij_max_jpg_bytes_sampled(out_w, out_h, sampling, 0);
   if (out_len) *out_len = bound;
-  if (cap < bound) return mij_fail(MIJ_ENOSPC, "mij_thumbnail: need %zu bytes for %dx%d", bound, out_w, out_h);
-  if (!out) return mij_fail(MIJ_EINVAL, "mij_thumbnail: out is NULL");
+  if (cap < bound) return mij_fail(MIJ_ENOSPC, "%s: need %zu bytes for %dx%d", what, bound, out_w, out_h);
+  if (!out) return mij_fail(MIJ_EINVAL, "%s: out is NULL", what);
   const int denom = mij_thumbnail_denom(w, h, out_w, out_h);
   const int dev = mij_drop_device();
   mij_decoder *d = nullptr;
@@ -621,7 +624,7 @@ extern "C" int mij_thumbnail(const uint8_t *jpg, size_t len, int out_w, int out_
     const void *px = mij_resizer_device_pixels(r, 0, &pitch);
     if (!px) return mij_last_error();
     if (int rc = mij_batch_pad_input(b, px, 0, pitch, wh, 1)) return rc;
-    if (int rc = mij_batch_encode_interleaved(b, 1, 0)) return rc;
+    if (int rc = sampling < 0 ? mij_batch_encode_interleaved(b, 1, 0) : mij_batch_encode_libjpeg(b, 1, sampling, 0)) return rc;
     size_t n = 0;
     if (int rc = mij_batch_output(b, 0, out, cap, &n)) return rc;
     if (out_len) *out_len = n;
@@ -634,4 +637,19 @@ extern "C" int mij_thumbnail(const uint8_t *jpg, size_t len, int out_w, int out_
   resizer_free(r);
   mij_decoder_destroy(d);
   return rc;
+}
+
+extern "C" int mij_thumbnail(const uint8_t *jpg, size_t len, int out_w, int out_h, int filter, int quality,
+                             uint8_t *out, size_t cap, size_t *out_len) {
+  return thumbnail("mij_thumbnail", jpg, len, out_w, out_h, filter, quality, -1, out, cap, out_len);
+}
+
+extern "C" int mij_thumbnail_libjpeg(const uint8_t *jpg, size_t len, int out_w, int out_h, int filter, int quality,
+                                     int sampling, uint8_t *out, size_t cap, size_t *out_len) {
+  if (sampling < MIJ_SAMP_420) {
+    mij_clear_error();
+    if (out_len) *out_len = 0;
+    return mij_fail(MIJ_EINVAL, "mij_thumbnail_libjpeg: sampling %d (MIJ_SAMP_420 .. MIJ_SAMP_GRAY)", sampling);
+  }
+  return thumbnail("mij_thumbnail_libjpeg", jpg, len, out_w, out_h, filter, quality, sampling, out, cap, out_len);
 }

@@ -9,9 +9,13 @@
  *
  *   encode_ppm <in.ppm> <out.jpg> [quality] [x y w h] [--fused]
  *   encode_ppm <in.ppm> <out.jpg> [quality] --sampling 444|422|420|gray
+ *   encode_ppm <in.ppm> <out.jpg> [quality] --libjpeg [--sampling 444|422|420|gray]
  *
  * With --sampling the PPM may have any size and becomes one standard
  * interleaved baseline stream at that chroma sampling (mij_encode_sampled).
+ * With --libjpeg the stream has libjpeg's quantisation tables and
+ * coefficients for that quality and sampling, 4:2:0 unless --sampling says
+ * otherwise (mij_encode_libjpeg).
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -63,10 +67,19 @@ static uint8_t *read_ppm_bgr(const char *path, int *w, int *h, int any_size) {
 int main(int argc, char **argv) {
     if (argc < 3) {
         fprintf(stderr, "usage: %s <in.ppm> <out.jpg> [quality] [x y w h] [--fused]\n"
-                        "       %s <in.ppm> <out.jpg> [quality] --sampling 444|422|420|gray\n", argv[0], argv[0]);
+                        "       %s <in.ppm> <out.jpg> [quality] --sampling 444|422|420|gray\n"
+                        "       %s <in.ppm> <out.jpg> [quality] --libjpeg [--sampling 444|422|420|gray]\n",
+                argv[0], argv[0], argv[0]);
         return 2;
     }
-    int fused = 0, sampling = -1;
+    int fused = 0, sampling = -1, libjpeg = 0;
+    for (int i = 3; i < argc; i++)
+        if (!strcmp(argv[i], "--libjpeg")) { /* the option leaves the argument list */
+            libjpeg = 1;
+            for (int j = i; j + 1 < argc; j++) argv[j] = argv[j + 1];
+            argc--;
+            break;
+        }
     for (int i = 3; i + 1 < argc; i++)
         if (!strcmp(argv[i], "--sampling")) { /* the option and its value leave the argument list */
             static const char *const names[4] = {"420", "422", "444", "gray"};
@@ -81,6 +94,7 @@ int main(int argc, char **argv) {
             break;
         }
     if (!strcmp(argv[argc - 1], "--fused")) { fused = 1; argc--; }
+    if (libjpeg && sampling < 0) sampling = MIJ_SAMP_420;
     int W, H;
     uint8_t *raw = read_ppm_bgr(argv[1], &W, &H, sampling >= 0);
     if (!raw) return 1;
@@ -88,14 +102,16 @@ int main(int argc, char **argv) {
     if (sampling >= 0) {
         size_t bound = mij_max_jpg_bytes_sampled(W, H, sampling, 0), n = 0;
         uint8_t *out = malloc(bound ? bound : 1);
-        if (!out || mij_encode_sampled(raw, W, W, H, MIJ_PIX_BGR, quality, sampling, 0, out, bound, &n) != MIJ_OK) {
+        if (!out || (libjpeg ? mij_encode_libjpeg : mij_encode_sampled)(raw, W, W, H, MIJ_PIX_BGR, quality, sampling, 0, out,
+                                                                         bound, &n) != MIJ_OK) {
             fprintf(stderr, "%s: %s\n", argv[1], mij_last_message());
             return 1;
         }
         FILE *f = fopen(argv[2], "wb");
         if (!f || fwrite(out, 1, n, f) != n) { perror(argv[2]); return 1; }
         fclose(f);
-        printf("%s: %dx%d Q=%d sampling %d -> %zu bytes\n", argv[2], W, H, quality, sampling, n);
+        printf("%s: %dx%d Q=%d sampling %d%s -> %zu bytes\n", argv[2], W, H, quality, sampling,
+               libjpeg ? ", libjpeg's arithmetic" : "", n);
         free(raw);
         free(out);
         return 0;

@@ -8,9 +8,13 @@
  * Image.resize does, encoded as mij_encode_any encodes (4:2:0, one scan).  The
  * pixels never leave the GPU (mij_thumbnail).
  *
- *   thumbnail_jpg [-filter box|bilinear|bicubic] [-quality Q] WxH <in.jpg> <out.jpg>
+ *   thumbnail_jpg [-filter box|bilinear|bicubic] [-quality Q] [--libjpeg [--sampling 444|422|420|gray]]
+ *                 WxH <in.jpg> <out.jpg>
  *
- * Defaults: bicubic, quality 75.
+ * Defaults: bicubic, quality 75.  With --libjpeg the last stage is
+ * mij_thumbnail_libjpeg: libjpeg's quantisation tables and coefficients for
+ * that quality, at the --sampling (4:2:0 unless given), the ones Pillow's
+ * draft -> resize -> save writes.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -42,16 +46,29 @@ static int fail(const char *what, int rc) {
 }
 
 static int usage(const char *prog) {
-    fprintf(stderr, "usage: %s [-filter box|bilinear|bicubic] [-quality Q] WxH <in.jpg> <out.jpg>\n", prog);
+    fprintf(stderr, "usage: %s [-filter box|bilinear|bicubic] [-quality Q] [--libjpeg [--sampling 444|422|420|gray]] "
+                    "WxH <in.jpg> <out.jpg>\n", prog);
     return 2;
 }
 
 int main(int argc, char **argv) {
     const char *prog = argv[0];
-    int filter = MIJ_RS_BICUBIC, quality = 75;
+    int filter = MIJ_RS_BICUBIC, quality = 75, libjpeg = 0, sampling = -1;
     while (argc > 2 && argv[1][0] == '-' && argv[1][1]) {
         const char *o = argv[1], *v = argv[2];
-        if (!strcmp(o, "-filter") && !strcmp(v, "box")) filter = MIJ_RS_BOX;
+        if (!strcmp(o, "--libjpeg")) { /* no value */
+            libjpeg = 1;
+            argc--;
+            argv++;
+            continue;
+        }
+        if (!strcmp(o, "--sampling")) {
+            static const char *const names[4] = {"420", "422", "444", "gray"};
+            for (int k = 0; k < 4; k++)
+                if (!strcmp(v, names[k])) sampling = k;
+            if (sampling < 0) return usage(prog);
+        }
+        else if (!strcmp(o, "-filter") && !strcmp(v, "box")) filter = MIJ_RS_BOX;
         else if (!strcmp(o, "-filter") && !strcmp(v, "bilinear")) filter = MIJ_RS_BILINEAR;
         else if (!strcmp(o, "-filter") && !strcmp(v, "bicubic")) filter = MIJ_RS_BICUBIC;
         else if (!strcmp(o, "-quality")) quality = atoi(v);
@@ -59,17 +76,25 @@ int main(int argc, char **argv) {
         argc -= 2;
         argv += 2;
     }
+    if (sampling >= 0 && !libjpeg) {
+        fprintf(stderr, "--sampling needs --libjpeg: the default arithmetic writes 4:2:0\n");
+        return 2;
+    }
+    if (sampling < 0) sampling = MIJ_SAMP_420;
     int ow = 0, oh = 0;
     if (argc != 4 || sscanf(argv[1], "%dx%d", &ow, &oh) != 2) return usage(prog);
     size_t len = 0, n = 0;
     uint8_t *jpg = read_file(argv[2], &len);
     if (!jpg) return 1;
     /* the output's bound: mij_thumbnail reports it with MIJ_ENOSPC before any device work */
-    int rc = mij_thumbnail(jpg, len, ow, oh, filter, quality, NULL, 0, &n);
+    int rc = libjpeg ? mij_thumbnail_libjpeg(jpg, len, ow, oh, filter, quality, sampling, NULL, 0, &n)
+                     : mij_thumbnail(jpg, len, ow, oh, filter, quality, NULL, 0, &n);
     if (rc != MIJ_ENOSPC) return fail(argv[2], rc);
     uint8_t *out = malloc(n);
     if (!out) { fprintf(stderr, "out of memory\n"); return 1; }
-    if ((rc = mij_thumbnail(jpg, len, ow, oh, filter, quality, out, n, &n)) != MIJ_OK) return fail(argv[2], rc);
+    rc = libjpeg ? mij_thumbnail_libjpeg(jpg, len, ow, oh, filter, quality, sampling, out, n, &n)
+                 : mij_thumbnail(jpg, len, ow, oh, filter, quality, out, n, &n);
+    if (rc != MIJ_OK) return fail(argv[2], rc);
     FILE *f = fopen(argv[3], "wb");
     if (!f || fwrite(out, 1, n, f) != n || fclose(f)) {
         perror(argv[3]);

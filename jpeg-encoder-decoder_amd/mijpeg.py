@@ -59,6 +59,7 @@ EXPORTS = [
     "mij_resizer_create", "mij_resizer_destroy", "mij_resizer_resize", "mij_resizer_device_pixels", "mij_resizer_pixels",
     "mij_resizer_ms", "mij_resizer_stream", "mij_resizer_set_stream", "mij_resize", "mij_thumbnail",
     "mij_thumbnail_denom",
+    "mij_libjpeg_tables", "mij_batch_encode_libjpeg", "mij_encode_libjpeg", "mij_thumbnail_libjpeg",
 ]
 
 
@@ -282,6 +283,10 @@ def load() -> C.CDLL:
         lib.mij_resize.argtypes = [p, i, i, i, i, i, i, p, sz]
         lib.mij_thumbnail.argtypes = [p, sz, i, i, i, i, p, sz, C.POINTER(sz)]
         lib.mij_thumbnail_denom.argtypes = [i, i, i, i]
+        lib.mij_libjpeg_tables.argtypes = [i, p]
+        lib.mij_batch_encode_libjpeg.argtypes = [p, i, i, i]
+        lib.mij_encode_libjpeg.argtypes = [p, i, i, i, i, i, i, i, p, sz, C.POINTER(sz)]
+        lib.mij_thumbnail_libjpeg.argtypes = [p, sz, i, i, i, i, i, p, sz, C.POINTER(sz)]
     except AttributeError:
         if not os.environ.get("MIJ_LIB"):  # older builds only in A/B timing runs
             raise
@@ -420,19 +425,54 @@ def max_jpg_bytes_sampled(w: int, h: int, sampling: str = "420", restart_rows: i
     return int(load().mij_max_jpg_bytes_sampled(w, h, _sampling(sampling), restart_rows))
 
 
+ARITHMETICS = ("reference", "libjpeg")
+
+
+def _arithmetic(arithmetic) -> bool:
+    if arithmetic not in ARITHMETICS:
+        raise ValueError(f"arithmetic {arithmetic!r}: one of {ARITHMETICS}")
+    return arithmetic == "libjpeg"
+
+
+def libjpeg_tables(quality: int) -> np.ndarray:
+    """mij_libjpeg_tables: (2, 64) uint8, the luma and the chroma table libjpeg
+    uses at a quality, zigzag order; host only"""
+    out = np.zeros((2, 64), np.uint8)
+    _check(load().mij_libjpeg_tables(int(quality), _ptr(out)), "mij_libjpeg_tables")
+    return out
+
+
 def encode_any(frame: np.ndarray, order: str = "bgr", quality: int = 50, restart_rows: int = 0,
                sampling: str = "420") -> bytes:
     """mij_encode_any: an (h, w, 3) frame of any size to a standard
     interleaved baseline stream, host to host; with sampling
-    "422", "444" or "gray" through mij_encode_sampled."""
+    "422", "444" or "gray" through mij_encode_sampled.
+    encode_libjpeg is the same call with libjpeg's arithmetic."""
+    return _encode_host(frame, order, quality, restart_rows, sampling, False)
+
+
+def encode_libjpeg(frame: np.ndarray, order: str = "bgr", quality: int = 75, restart_rows: int = 0,
+                   sampling: str = "420") -> bytes:
+    """mij_encode_libjpeg: encode_any with libjpeg's tables and coefficients
+    for that quality and sampling, host to host"""
+    return _encode_host(frame, order, quality, restart_rows, sampling, True)
+
+
+def _encode_host(frame, order, quality, restart_rows, sampling, libjpeg) -> bytes:
     lib = load()
     frame = np.ascontiguousarray(frame, np.uint8)
     h, w = frame.shape[:2]
     n = C.c_size_t(0)
-    if _sampling(sampling):
+    samp = _sampling(sampling)
+    if libjpeg:
         def call(px, out, cap):
-            return lib.mij_encode_sampled(px, w, w, h, PIXEL_ORDERS[order], quality, SAMPLINGS[sampling],
-                                          restart_rows, out, cap, C.byref(n))
+            return lib.mij_encode_libjpeg(px, w, w, h, PIXEL_ORDERS[order], quality, samp, restart_rows, out, cap,
+                                          C.byref(n))
+        what = "mij_encode_libjpeg"
+    elif samp:
+        def call(px, out, cap):
+            return lib.mij_encode_sampled(px, w, w, h, PIXEL_ORDERS[order], quality, samp, restart_rows, out, cap,
+                                          C.byref(n))
         what = "mij_encode_sampled"
     else:
         def call(px, out, cap):
@@ -548,8 +588,14 @@ class Batch:
         mij_batch_encode_sampled); restart_rows counts MCU rows of that sampling"""
         _check(self.lib.mij_batch_encode_sampled(self.h_, n, _sampling(sampling), restart_rows), "encode_sampled")
 
+    def encode_libjpeg(self, n: int, sampling: str = "420", restart_rows: int = 0) -> None:
+        """encode_sampled with libjpeg's arithmetic and the batch's quality on
+        its scale (mij_batch_encode_libjpeg), 4:2:0 included"""
+        _check(self.lib.mij_batch_encode_libjpeg(self.h_, n, _sampling(sampling), restart_rows), "encode_libjpeg")
+
     def sampled_layout(self, frame: int) -> dict:
-        """mij_batch_sampled_layout: the geometry the last encode_sampled coded, as Decoder.layout gives it"""
+        """mij_batch_sampled_layout: the geometry the last encode_sampled or encode_libjpeg coded, as
+        Decoder.layout gives it"""
         out = np.zeros(24, np.int32)
         _check(self.lib.mij_batch_sampled_layout(self.h_, frame, _ptr(out), out.size), "sampled_layout")
         v = [int(x) for x in out]
@@ -1353,14 +1399,26 @@ def resize(frame: np.ndarray, size, filter="bicubic") -> np.ndarray:
     return out
 
 
-def thumbnail(jpg: bytes, size, filter="bicubic", quality: int = 75) -> bytes:
+def thumbnail(jpg: bytes, size, filter="bicubic", quality: int = 75, arithmetic: str = "reference",
+              sampling: str = "420") -> bytes:
     """mij_thumbnail: one baseline stream -> a JPEG of exactly size = (w, h):
     decoded at thumbnail_denom, resized, encoded as encode_any encodes; the
-    pixels never leave the device"""
+    pixels never leave the device.  arithmetic "libjpeg": through
+    mij_thumbnail_libjpeg at `sampling`, the coefficients Pillow's draft ->
+    resize -> save(quality, subsampling) gives; with the
+    default arithmetic the sampling is 4:2:0 and nothing else."""
     lib = load()
     buf = np.frombuffer(jpg, np.uint8)
     ow, oh = int(size[0]), int(size[1])
     n = C.c_size_t(0)
+    samp = _sampling(sampling)
+    if _arithmetic(arithmetic):
+        out = np.zeros(max(int(lib.mij_max_jpg_bytes_sampled(ow, oh, samp, 0)), 1), np.uint8)
+        _check(lib.mij_thumbnail_libjpeg(_ptr(buf), buf.size, ow, oh, _filter(filter), int(quality), samp, _ptr(out),
+                                         out.nbytes, C.byref(n)), "mij_thumbnail_libjpeg")
+        return out[:n.value].tobytes()
+    if samp:
+        raise ValueError(f"thumbnail: sampling {sampling!r} needs arithmetic=\"libjpeg\"")
     out = np.zeros(max(int(lib.mij_max_jpg_bytes_any(ow, oh, 0)), 1), np.uint8)
     _check(lib.mij_thumbnail(_ptr(buf), buf.size, ow, oh, _filter(filter), int(quality), _ptr(out), out.nbytes,
                              C.byref(n)), "mij_thumbnail")
