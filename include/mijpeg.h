@@ -774,6 +774,98 @@ int mij_thumbnail_libjpeg(const uint8_t *jpg, size_t len, int out_w, int out_h, 
  * out_w, h / out_h) in integer division, 1 if none is (and for sizes < 1) */
 int mij_thumbnail_denom(int w, int h, int out_w, int out_h);   /* host only */
 
+/* ---- pixels to tensors ----------------------------------------
+ * The last stage of an input pipeline: n device images of 3-byte pixels, all
+ * of one size w x h, into ONE dense tensor [n, 3, h, w] (MIJ_T_NCHW) or
+ * [n, h, w, 3] (MIJ_T_NHWC) in caller-owned device memory, for instance a
+ * torch tensor's data_ptr().  The element tensor channel c gets for source
+ * byte v is torchvision's to_tensor followed by normalize, in IEEE single
+ * precision, round to nearest even:
+ *     t = (float)v / 255.0f;   t = t - mean[c];   t = t / std[c];
+ * MIJ_T_F32 stores t, MIJ_T_F16 / MIJ_T_BF16 t rounded to nearest even (what
+ * tensor.to(torch.float16 / torch.bfloat16) gives), MIJ_T_U8 stores v (mean
+ * and std are not read).  The values come from a table built on the host, so
+ * they are the same bits on every device.  swap = 1: tensor channel c reads
+ * pixel byte 2 - c (BGR pixels, RGB tensor).  mirror: one flag per frame (NULL:
+ * none); output column x of a flagged frame reads source column w - 1 - x.
+ *
+ * A source image is what mij_resizer_resize takes: any device pointer, any
+ * pitch >= 3 * w, read in whole aligned 4-byte words that hold at least one
+ * byte of the image's rows.  d_dst is 16-byte aligned and holds
+ * mij_tensor_bytes(n, w, h, dtype) bytes.  The run is asynchronous on the
+ * tensorizer's stream.  d_dst == NULL: the tensor goes to a buffer the
+ * tensorizer owns (it grows on demand; cap_bytes is not read), served by
+ * mij_tensorizer_device and mij_tensorizer_read until the next such run.
+ *
+ * Refused with MIJ_EINVAL before any device work, the message naming the frame
+ * and the argument, decided in this order: an unknown dtype or layout; swap
+ * outside 0 / 1; for the float dtypes a mean that is not finite or a std that
+ * is 0 or not finite; a null src; n outside 1..max_frames; per frame a null
+ * image, a size outside 1..65535, a pitch under 3 * w, a size other than
+ * frame 0's; a d_dst that is not 16-byte aligned; then MIJ_ENOSPC for
+ * cap_bytes under mij_tensor_bytes (the message gives the need: a cap of 0
+ * asks for it); a null tensorizer last.  A refused call leaves the previous
+ * owned result served. */
+enum { MIJ_T_U8 = 0, MIJ_T_F16 = 1, MIJ_T_BF16 = 2, MIJ_T_F32 = 3 };
+enum { MIJ_T_NCHW = 0, MIJ_T_NHWC = 1 };
+typedef struct { int dtype, layout, swap; float mean[3], std[3]; } mij_tensor_spec;
+typedef struct mij_tensorizer mij_tensorizer;
+mij_tensorizer *mij_tensorizer_create(int device, int max_frames);
+void mij_tensorizer_destroy(mij_tensorizer *t);
+int mij_tensorizer_run(mij_tensorizer *t, const mij_image *src, const uint8_t *mirror /* n flags or NULL */,
+                       int n, const mij_tensor_spec *spec, void *d_dst, size_t cap_bytes);
+/* bytes of the tensor; 0 for n < 1, a size outside 1..65535, an unknown dtype */
+size_t mij_tensor_bytes(int n, int w, int h, int dtype);   /* host only */
+/* the owned buffer of the last run with d_dst == NULL and its size; complete
+ * once the tensorizer's stream has reached this point; NULL (MIJ_EINVAL)
+ * before such a run */
+void *mij_tensorizer_device(mij_tensorizer *t, size_t *bytes);
+/* host copy of it; MIJ_ENOSPC for a short cap; waits */
+int mij_tensorizer_read(mij_tensorizer *t, void *dst, size_t cap);
+int mij_tensorizer_ms(mij_tensorizer *t, float *ms);       /* HIP-event time of the last run; waits */
+void *mij_tensorizer_stream(mij_tensorizer *t);
+int mij_tensorizer_set_stream(mij_tensorizer *t, void *stream);  /* as mij_batch_set_stream */
+
+/* The chain that ends in it: n stored JPEGs to one tensor.  A loader owns a
+ * decoder (for streams up to max_w x max_h), a resizer and a tensorizer on one
+ * stream.  mij_loader_load:
+ *   decode     the n streams, of any accepted kind and differing sizes, in one
+ *              mij_decoder_decode;
+ *   scale      one mij_decoder_reconstruct_scaled(order, d) for the call:
+ *              d = denom (1, 2, 4, 8), or with denom 0 the smallest
+ *              mij_thumbnail_denom(crop w, crop h, out_w, out_h) over the
+ *              frames, so that no frame is enlarged from fewer samples than
+ *              it needs (mij_loader_denom gives the last call's d);
+ *   crop       crops[i] = (x, y, w, h) in full-size pixels, inside the frame,
+ *              w, h >= 1 (NULL: whole frames) becomes the scaled image's
+ *              rectangle x0 = x / d, y0 = y / d, x1 = min(ceil(W / d),
+ *              ceil((x + w) / d)), y1 likewise;
+ *   resize     every rectangle to out_w x out_h with `filter` (MIJ_RS_*) in
+ *              one mij_resizer_resize;
+ *   tensorize  the results into d_dst (or the owned buffer) as
+ *              mij_tensorizer_run does, with its spec, mirror flags, cap and
+ *              refusals.
+ * Asynchronous from the reconstruct on, on mij_loader_stream.  Refused before
+ * any device work: what mij_decode refuses of a stream's headers, with its
+ * code and message; MIJ_EINVAL for a bad spec, n, out size, filter, denom,
+ * order, a stream larger than the loader's, a crop that is empty or outside
+ * its frame, a misaligned d_dst; MIJ_ENOSPC for a short cap; a null loader
+ * last. */
+typedef struct mij_loader mij_loader;
+mij_loader *mij_loader_create(int device, int max_w, int max_h, int max_frames);
+void mij_loader_destroy(mij_loader *l);
+int mij_loader_load(mij_loader *l, const uint8_t *const *jpgs, const size_t *lens, int n,
+                    const area_t *crops /* n, full-size pixels, or NULL */, const uint8_t *mirror,
+                    int out_w, int out_h, int filter, int denom /* 1,2,4,8; 0 = auto */,
+                    int order, const mij_tensor_spec *spec, void *d_dst, size_t cap_bytes);
+int mij_loader_denom(mij_loader *l);                       /* of the last load; 0 before one */
+void *mij_loader_device(mij_loader *l, size_t *bytes);     /* as mij_tensorizer_device */
+int mij_loader_read(mij_loader *l, void *dst, size_t cap); /* as mij_tensorizer_read */
+/* {entropy decode (mij_decoder_decode's span on the stream, its host parsing
+ * included), reconstruct, resize, tensorize} of the last load, ms; waits */
+int mij_loader_ms(mij_loader *l, float ms[4]);
+void *mij_loader_stream(mij_loader *l);
+
 /* ---- lossless transcoding ------------------------------------
  * What jpegtran -optimize does, on the GPU: every frame of the last decode,
  * of either kind above, becomes one standard interleaved baseline stream

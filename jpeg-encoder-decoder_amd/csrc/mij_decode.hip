@@ -2156,6 +2156,15 @@ extern "C" int mij_decoder_transcode_ms(mij_decoder *d, float *ms) {
 
 extern "C" void *mij_decoder_stream(mij_decoder *d) { return d ? (void *)d->stream : nullptr; }
 
+// for the other host translation units (mij_host.h): the headers alone
+int mij_parse_size(const char *what, const uint8_t *jpg, size_t len, int frame, int *w, int *h) {
+  Parsed P;
+  if (int rc = parse(jpg, len, P, frame)) return mij_fail(rc, "%s: %s", what, P.err);
+  *w = P.w;
+  *h = P.h;
+  return MIJ_OK;
+}
+
 extern "C" int mij_decode(const uint8_t *jpg, size_t len, int order, uint8_t *out, size_t cap, int *w, int *h) {
   mij_clear_error();
   if (!jpg || !out) return mij_fail(MIJ_EINVAL, "mij_decode: NULL buffer");

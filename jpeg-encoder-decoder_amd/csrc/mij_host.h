@@ -22,6 +22,10 @@ int mij_batch_upload_slot_async(mij_batch *b, const uint8_t *host, int slot, voi
 int mij_batch_lengths_async(mij_batch *b, uint64_t *h_len, int *h_err, int nframes);
 int mij_batch_output_async(mij_batch *b, int frame, uint8_t *dst, size_t n);
 
+// the size in a stream's headers, parsed as mij_decoder_decode parses stream `frame` of a call: no device
+// work; what the decoder refuses is refused here, with its code and message (mij_decode.hip)
+int mij_parse_size(const char *what, const uint8_t *jpg, size_t len, int frame, int *w, int *h);
+
 // drop-in state shared with the detector's drop-in calls (mij_detect.hip)
 int mij_drop_stride();   // define.h:3 WIDTH, as set by mij_set_input_stride
 int mij_drop_device();   // MIJ_DEVICE or 0

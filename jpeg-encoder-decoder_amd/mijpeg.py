@@ -60,6 +60,10 @@ EXPORTS = [
     "mij_resizer_ms", "mij_resizer_stream", "mij_resizer_set_stream", "mij_resize", "mij_thumbnail",
     "mij_thumbnail_denom",
     "mij_libjpeg_tables", "mij_batch_encode_libjpeg", "mij_encode_libjpeg", "mij_thumbnail_libjpeg",
+    "mij_tensorizer_create", "mij_tensorizer_destroy", "mij_tensorizer_run", "mij_tensor_bytes", "mij_tensorizer_device",
+    "mij_tensorizer_read", "mij_tensorizer_ms", "mij_tensorizer_stream", "mij_tensorizer_set_stream",
+    "mij_loader_create", "mij_loader_destroy", "mij_loader_load", "mij_loader_denom", "mij_loader_device",
+    "mij_loader_read", "mij_loader_ms", "mij_loader_stream",
 ]
 
 
@@ -287,6 +291,32 @@ def load() -> C.CDLL:
         lib.mij_batch_encode_libjpeg.argtypes = [p, i, i, i]
         lib.mij_encode_libjpeg.argtypes = [p, i, i, i, i, i, i, i, p, sz, C.POINTER(sz)]
         lib.mij_thumbnail_libjpeg.argtypes = [p, sz, i, i, i, i, i, p, sz, C.POINTER(sz)]
+        lib.mij_tensorizer_create.restype = p
+        lib.mij_tensorizer_create.argtypes = [i, i]
+        lib.mij_tensorizer_destroy.restype = None
+        lib.mij_tensorizer_destroy.argtypes = [p]
+        lib.mij_tensorizer_run.argtypes = [p, p, p, i, p, p, sz]
+        lib.mij_tensor_bytes.restype = sz
+        lib.mij_tensor_bytes.argtypes = [i, i, i, i]
+        lib.mij_tensorizer_device.restype = p
+        lib.mij_tensorizer_device.argtypes = [p, C.POINTER(sz)]
+        lib.mij_tensorizer_read.argtypes = [p, p, sz]
+        lib.mij_tensorizer_ms.argtypes = [p, C.POINTER(C.c_float)]
+        lib.mij_tensorizer_stream.restype = p
+        lib.mij_tensorizer_stream.argtypes = [p]
+        lib.mij_tensorizer_set_stream.argtypes = [p, p]
+        lib.mij_loader_create.restype = p
+        lib.mij_loader_create.argtypes = [i, i, i, i]
+        lib.mij_loader_destroy.restype = None
+        lib.mij_loader_destroy.argtypes = [p]
+        lib.mij_loader_load.argtypes = [p, C.POINTER(p), C.POINTER(sz), i, p, p, i, i, i, i, i, p, p, sz]
+        lib.mij_loader_denom.argtypes = [p]
+        lib.mij_loader_device.restype = p
+        lib.mij_loader_device.argtypes = [p, C.POINTER(sz)]
+        lib.mij_loader_read.argtypes = [p, p, sz]
+        lib.mij_loader_ms.argtypes = [p, p]
+        lib.mij_loader_stream.restype = p
+        lib.mij_loader_stream.argtypes = [p]
     except AttributeError:
         if not os.environ.get("MIJ_LIB"):  # older builds only in A/B timing runs
             raise
@@ -1488,3 +1518,217 @@ class Resizer:
     def set_stream(self, stream) -> None:
         """run on the caller's hipStream_t (0 / None: the resizer's own), as Batch.set_stream"""
         _check(self.lib.mij_resizer_set_stream(self.h_, stream or None), "resizer_set_stream")
+
+
+# ---- pixels to tensors (DESIGN.md §4o) -----------------------------------------
+# MIJ_T_*: name -> (code, numpy dtype of the host copy; bfloat16 comes back as its uint16 bit patterns)
+T_DTYPES = {"uint8": (0, np.uint8), "float16": (1, np.float16), "bfloat16": (2, np.uint16), "float32": (3, np.float32)}
+T_LAYOUTS = {"nchw": 0, "nhwc": 1}
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+
+
+class TensorSpec(C.Structure):
+    """mij_tensor_spec"""
+    _fields_ = [("dtype", C.c_int), ("layout", C.c_int), ("swap", C.c_int), ("mean", C.c_float * 3),
+                ("std", C.c_float * 3)]
+
+
+def _dtype(dtype) -> int:
+    if isinstance(dtype, str):
+        if dtype not in T_DTYPES:
+            raise MijError(f"dtype {dtype!r}: one of {', '.join(T_DTYPES)}")
+        return T_DTYPES[dtype][0]
+    return int(dtype)
+
+
+def _spec(dtype, layout, swap, mean, std) -> TensorSpec:
+    if isinstance(layout, str):
+        if layout not in T_LAYOUTS:
+            raise MijError(f"layout {layout!r}: one of {', '.join(T_LAYOUTS)}")
+        layout = T_LAYOUTS[layout]
+    return TensorSpec(_dtype(dtype), int(layout), int(swap), (C.c_float * 3)(*[float(v) for v in mean]),
+                      (C.c_float * 3)(*[float(v) for v in std]))
+
+
+def tensor_bytes(n: int, w: int, h: int, dtype="float16") -> int:
+    """mij_tensor_bytes: bytes of an [n, 3, h, w] tensor of `dtype`; 0 for bad arguments; host only"""
+    return int(load().mij_tensor_bytes(int(n), int(w), int(h), _dtype(dtype)))
+
+
+def _shape(n: int, w: int, h: int, layout: int):
+    return (n, h, w, 3) if layout == T_LAYOUTS["nhwc"] else (n, 3, h, w)
+
+
+def _host_tensor(read, spec: TensorSpec, n: int, w: int, h: int) -> np.ndarray:
+    """the owned buffer's host copy, through read(address, bytes)"""
+    np_dtype = next(v[1] for v in T_DTYPES.values() if v[0] == spec.dtype)
+    out = np.zeros(_shape(n, w, h, spec.layout), np_dtype)
+    read(_ptr(out), out.nbytes)
+    return out
+
+
+def _out_target(out, spec: TensorSpec, dtype, n: int, w: int, h: int):
+    """(address, bytes) of a caller's tensor: anything with data_ptr(),
+    element_size(), numel() and is_contiguous(), such as a torch tensor on the
+    library's device; refused when it is short, strided or of another dtype"""
+    need = tensor_bytes(n, w, h, spec.dtype)
+    es = need // max(3 * n * w * h, 1)
+    if not out.is_contiguous():
+        raise MijError("out: not contiguous")
+    name = str(getattr(out, "dtype", ""))
+    if out.element_size() != es or (isinstance(dtype, str) and name and name.split(".")[-1] != dtype):
+        raise MijError(f"out: dtype {name or out.element_size()} where {dtype} ({es} bytes an element) is asked for")
+    if out.numel() * es < need:
+        raise MijError(f"out: {out.numel()} elements where {need // es} are needed")
+    return int(out.data_ptr()), out.numel() * es
+
+
+class Tensorizer:
+    """Device images of one size -> one dense normalised tensor
+    (mij_tensorizer_*): torchvision's to_tensor + normalize, bit for bit, all
+    frames of a call in one launch."""
+
+    def __init__(self, max_frames: int, device: int = 0):
+        self.lib = load()
+        self.last_ = None
+        self.h_ = self.lib.mij_tensorizer_create(device, max_frames)
+        if not self.h_:
+            raise MijError("mij_tensorizer_create failed: "
+                           f"{self.lib.mij_strerror(self.lib.mij_last_error()).decode()}: "
+                           f"{self.lib.mij_last_message().decode(errors='replace')}")
+
+    def close(self) -> None:
+        if self.h_:
+            self.lib.mij_tensorizer_destroy(self.h_)
+            self.h_ = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, images, mirror=None, dtype="float16", layout="nchw", mean=IMAGENET_MEAN, std=IMAGENET_STD,
+            swap: bool = False, out=None, dst_ptr: int = 0, cap: int = 0):
+        """images: (device address, pitch, w, h) each, one size; mirror: a
+        flag per image or None.  out (a tensor, see Loader.load) or dst_ptr +
+        cap (a raw device address): written there, asynchronously on the
+        tensorizer's stream; neither: into the tensorizer's own buffer, read
+        with result()"""
+        n = len(images)
+        src = (Image * max(n, 1))(*[Image(int(a), int(pitch), int(w), int(h)) for a, pitch, w, h in images])
+        flags = None if mirror is None else (C.c_uint8 * max(n, 1))(*[1 if m else 0 for m in mirror])
+        spec = _spec(dtype, layout, swap, mean, std)
+        w, h = (int(images[0][2]), int(images[0][3])) if n else (0, 0)
+        if out is not None:
+            dst_ptr, cap = _out_target(out, spec, dtype, n, w, h)
+        _check(self.lib.mij_tensorizer_run(self.h_, src, flags, n, C.byref(spec), dst_ptr or None, cap), "tensorizer_run")
+        if not dst_ptr:
+            self.last_ = (spec, n, w, h)
+        return out
+
+    def result(self) -> np.ndarray:
+        """host copy of the last run into the tensorizer's own buffer; waits"""
+        if self.last_ is None:
+            _check(self.lib.mij_tensorizer_read(self.h_, None, 0), "tensorizer_read")
+        return _host_tensor(lambda a, nb: _check(self.lib.mij_tensorizer_read(self.h_, a, nb), "tensorizer_read"),
+                            *self.last_)
+
+    def device(self):
+        """(device address, bytes) of the own buffer's tensor"""
+        nb = C.c_size_t(0)
+        ptr = self.lib.mij_tensorizer_device(self.h_, C.byref(nb))
+        if not ptr:
+            _check(self.lib.mij_last_error() or 1, "tensorizer_device")
+        return int(ptr), int(nb.value)
+
+    def ms(self) -> float:
+        """HIP-event milliseconds of the last run; waits for it"""
+        ms = C.c_float(0)
+        _check(self.lib.mij_tensorizer_ms(self.h_, C.byref(ms)), "tensorizer_ms")
+        return float(ms.value)
+
+    def stream_ptr(self) -> int:
+        return int(self.lib.mij_tensorizer_stream(self.h_) or 0)
+
+    def set_stream(self, stream) -> None:
+        """run on the caller's hipStream_t (0 / None: the tensorizer's own), as Batch.set_stream"""
+        _check(self.lib.mij_tensorizer_set_stream(self.h_, stream or None), "tensorizer_set_stream")
+
+
+class Loader:
+    """Stored JPEGs -> one normalised tensor on the device (mij_loader_*):
+    decode at a scale, crop, resize, tensorize, on one stream."""
+
+    def __init__(self, max_w: int, max_h: int, max_frames: int, device: int = 0):
+        self.lib = load()
+        self.last_ = None
+        self.h_ = self.lib.mij_loader_create(device, max_w, max_h, max_frames)
+        if not self.h_:
+            raise MijError("mij_loader_create failed: "
+                           f"{self.lib.mij_strerror(self.lib.mij_last_error()).decode()}: "
+                           f"{self.lib.mij_last_message().decode(errors='replace')}")
+
+    def close(self) -> None:
+        if self.h_:
+            self.lib.mij_loader_destroy(self.h_)
+            self.h_ = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def load(self, jpgs, size, crops=None, mirror=None, filter="bilinear", scale: int = 0, dtype="float16",
+             layout="nchw", mean=IMAGENET_MEAN, std=IMAGENET_STD, order="rgb", out=None):
+        """jpgs: the streams; size = (w, h) of every output frame; crops: an
+        (x, y, w, h) in full-size pixels per stream, or None; mirror: a flag
+        per stream, or None; scale: the decode's denominator 1, 2, 4, 8, or 0:
+        the largest that enlarges no frame (denom() tells).  out=None: the
+        tensor as a numpy array from the loader's own buffer (bfloat16 as
+        uint16 bit patterns).  out: an object with data_ptr(), element_size(),
+        numel() and is_contiguous() (a torch tensor on the loader's device):
+        written there on the loader's stream, and returned; synchronise
+        (sync(), or torch.cuda.synchronize()) before reading it."""
+        n = len(jpgs)
+        bufs = [np.frombuffer(s, np.uint8) for s in jpgs]
+        ptrs = (C.c_void_p * max(n, 1))(*[_ptr(b) for b in bufs])
+        lens = (C.c_size_t * max(n, 1))(*[len(s) for s in jpgs])
+        areas = None if crops is None else (Area * max(n, 1))(*[Area(*[int(v) for v in c]) for c in crops])
+        flags = None if mirror is None else (C.c_uint8 * max(n, 1))(*[1 if m else 0 for m in mirror])
+        spec = _spec(dtype, layout, False, mean, std)
+        w, h = int(size[0]), int(size[1])
+        dst_ptr, cap = _out_target(out, spec, dtype, n, w, h) if out is not None else (0, 0)
+        _check(self.lib.mij_loader_load(self.h_, ptrs, lens, n, areas, flags, w, h, _filter(filter), int(scale),
+                                        _order(order), C.byref(spec), dst_ptr or None, cap), "loader_load")
+        if out is not None:
+            return out
+        self.last_ = (spec, n, w, h)
+        return _host_tensor(lambda a, nb: _check(self.lib.mij_loader_read(self.h_, a, nb), "loader_read"), *self.last_)
+
+    def denom(self) -> int:
+        """the denominator the last load decoded at"""
+        return int(self.lib.mij_loader_denom(self.h_))
+
+    def device(self):
+        """(device address, bytes) of the own buffer's tensor"""
+        nb = C.c_size_t(0)
+        ptr = self.lib.mij_loader_device(self.h_, C.byref(nb))
+        if not ptr:
+            _check(self.lib.mij_last_error() or 1, "loader_device")
+        return int(ptr), int(nb.value)
+
+    def ms(self):
+        """(entropy decode, reconstruct, resize, tensorize) milliseconds of the last load; waits for it"""
+        ms = (C.c_float * 4)()
+        _check(self.lib.mij_loader_ms(self.h_, ms), "loader_ms")
+        return tuple(float(v) for v in ms)
+
+    def sync(self) -> None:
+        """waits for the last load (its tensorize stage's end)"""
+        self.ms()
+
+    def stream_ptr(self) -> int:
+        return int(self.lib.mij_loader_stream(self.h_) or 0)
