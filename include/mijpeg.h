@@ -621,6 +621,42 @@ int mij_decoder_passes(mij_decoder *d);
 /* device address of stream `frame`'s planes (Y, then Cb, then Cr) */
 void *mij_decoder_device_coefs(mij_decoder *d, int frame);
 
+/* ---- progressive files -----------------------------------------
+ * Opt-in: with MIJ_ACCEPT_PROGRESSIVE set, mij_decoder_decode (and the
+ * loader's decoder) also takes 8-bit Huffman progressive streams (SOF2),
+ * greyscale or YCbCr under the sampling and Adobe rules of the baseline
+ * files below, up to 64 scans, DC and AC Huffman table ids 0..3, DHT and DRI
+ * between scans, restart intervals counted in each scan's own MCUs.  The
+ * scan script must be legal and complete (T.81 G.1.1.1): MIJ_EJPEG names the
+ * stream, the scan and the rule otherwise, before any device work.  Each
+ * restart interval of each scan is decoded sequentially by one GPU wave (one
+ * lane of it working) into the same arena, scans that depend on each other in successive launches
+ * ("levels"); afterwards the frame is served exactly as an interleaved
+ * baseline frame without restart intervals: layout, component, reconstruct
+ * at every scale, transcode and transform work unchanged, and one call may
+ * mix all three kinds of stream.  Corrupt entropy data gives MIJ_EJPEG,
+ * "stream %d scan %d: corrupt entropy data (code)": 5 the bits end early,
+ * 6 invalid code, 8 an end-of-band run past its restart interval, 9 a
+ * coefficient index past Se.
+ * The mask holds until changed and is 0 at creation: with the bit clear
+ * nothing differs from a library without it, SOF2 is refused as not
+ * baseline.  Unknown bits: MIJ_EINVAL, the mask unchanged.  The one-shot
+ * calls (mij_decode, mij_decode_scaled, mij_transcode, mij_transform,
+ * mij_thumbnail*) always refuse SOF2. */
+#define MIJ_ACCEPT_PROGRESSIVE 1
+int mij_decoder_accept(mij_decoder *d, unsigned mask);
+/* of stream `frame` of the last decode (any pointer may be NULL): 1 if it was
+ * progressive; its scans (a baseline file: 1, the encoder's shape: 3); the
+ * dependent launches its scans were sorted into (not progressive: 1).
+ * mij_decoder_passes counts self-synchronising passes only: 0 for a call of
+ * progressive streams alone. */
+int mij_decoder_scan_info(mij_decoder *d, int frame, int *progressive, int *nscans, int *levels);
+/* Host only: width and height from the frame header (SOFn of any kind, found
+ * in front of the first SOS; no other rule is applied), for sizing a decoder
+ * before a stream that the one-shot calls refuse.  1 if found, else 0 with
+ * *w and *h untouched (either may be NULL). */
+int mij_jpeg_size(const uint8_t *jpg, size_t len, int *w, int *h);
+
 /* ---- ordinary baseline files -------------------------------------------------
  * mij_decoder_decode also accepts what libjpeg, Pillow, cameras and browsers
  * write: 8-bit baseline (SOF0, Huffman), greyscale or YCbCr with luma 1x1
@@ -859,6 +895,7 @@ int mij_loader_load(mij_loader *l, const uint8_t *const *jpgs, const size_t *len
                     int out_w, int out_h, int filter, int denom /* 1,2,4,8; 0 = auto */,
                     int order, const mij_tensor_spec *spec, void *d_dst, size_t cap_bytes);
 int mij_loader_denom(mij_loader *l);                       /* of the last load; 0 before one */
+int mij_loader_accept(mij_loader *l, unsigned mask);       /* mij_decoder_accept of the loader's decoder */
 void *mij_loader_device(mij_loader *l, size_t *bytes);     /* as mij_tensorizer_device */
 int mij_loader_read(mij_loader *l, void *dst, size_t cap); /* as mij_tensorizer_read */
 /* {entropy decode (mij_decoder_decode's span on the stream, its host parsing

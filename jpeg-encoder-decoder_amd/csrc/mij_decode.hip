@@ -18,7 +18,10 @@
 // block (DESIGN.md "Decoding ordinary baseline files").  Refused with MIJ_EJPEG and
 // the reason: SOF1..15, 12-bit samples, 16-bit DQT, 2 or 4 components, Adobe
 // RGB / YCCK, other sampling, further scans, Ss/Se/AhAl other than 0/63/0,
-// missing tables, restart markers missing or out of order.
+// missing tables, restart markers missing or out of order.  (c) Opt-in
+// (mij_decoder_accept): progressive streams, parsed by mij_progressive.h and
+// decoded by mij_progressive.hip into the same arena; this
+// file stages their scans and describes the result as a frame of shape (b).
 //
 // Host: marker parsing (SOI, APPn, DQT, DHT, DRI, SOF0, SOS, EOI), canonical
 // Huffman tables with a 9-bit lookahead, and the scans copied unstuffed
@@ -36,11 +39,14 @@
 
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <thread>
 #include <vector>
 
 #include "mij_host.h"
+#include "mij_huff.h"
 #include "mij_pixels.h"
+#include "mij_progressive.h"
 #include "mij_transcode.h"
 #include "mij_transform.h"
 
@@ -53,74 +59,10 @@
 
 namespace mij {
 
-constexpr int LOOK = 9;
-
-// One canonical Huffman table (ISO/IEC 10918-1 F.2.2.3 decoding procedure).
-struct DecTab {
-  uint16_t look[1 << LOOK];  // (length << 8) | symbol, 0 = longer than LOOK
-  int32_t maxcode[18];       // largest code of each length, -1 if none
-  int32_t valoff[17];        // index of the first symbol of a length - its code
-  uint8_t val[256];
-};
-
 // chunk c of a scan covers bits [c*CHUNK, (c+1)*CHUNK): a symbol belongs to
 // the chunk its first bit lies in.  512: measured against 1024 / 2048 / 4096
 // on 256 config-3 streams, 16.3 / 17.7 / 21.1 / 23.9 ms per decode call.
 constexpr int CHUNK = 512;
-
-// MSB-first bit window over an unstuffed, 8-byte aligned, zero-padded scan
-struct Bits {
-  const unsigned long long *w;
-  long long cw = -2;  // index of the word pair held (none yet)
-  unsigned long long hi = 0, lo = 0;
-  __device__ unsigned long long window(long long pos) {
-    const long long i = pos >> 6;
-    if (i != cw) {
-      if (i == cw + 1) {
-        hi = lo;
-        lo = __builtin_bswap64(w[i + 1]);
-      } else {
-        hi = __builtin_bswap64(w[i]);
-        lo = __builtin_bswap64(w[i + 1]);
-      }
-      cw = i;
-    }
-    const int sh = pos & 63;
-    return sh ? (hi << sh) | (lo >> (64 - sh)) : hi;
-  }
-};
-
-// one symbol (+ its magnitude bits) at pos; returns bits consumed, or 0 on
-// an invalid code.  F.2.2.3 DECODE with a LOOK-bit table, F.2.2.1 EXTEND
-__device__ __forceinline__ int decode_one(Bits &br, long long pos, const DecTab &t, int &sym, int &val) {
-  const unsigned long long win = br.window(pos);
-  int len;
-  const uint32_t e = t.look[win >> (64 - LOOK)];
-  if (e) {
-    len = e >> 8;
-    sym = e & 255;
-  } else {
-    len = 0;
-    for (int l = LOOK + 1; l <= 16; l++) {
-      const int32_t code = (int32_t)(win >> (64 - l));
-      if (code <= t.maxcode[l]) {
-        len = l;
-        sym = t.val[t.valoff[l] + code];
-        break;
-      }
-    }
-    if (!len) return 0;
-  }
-  const int s = sym & 15;
-  if (s) {
-    // magnitude bits follow the code; the window holds >= 64 - 16 bits
-    const int v = (int)((win << len) >> (64 - s));
-    val = v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;  // negatives are ~|v| (encoder.c:442-444)
-  } else {
-    val = 0;
-  }
-  return len + s;
-}
 
 // the last entry of a table sorted by KEY whose KEY is <= v (entry 0 if none is)
 template <auto KEY, class T>
@@ -703,6 +645,7 @@ struct Parsed {
     long long data, end;  // raw bytes of one restart interval
   };
   std::vector<Ivl> ivl;
+  std::shared_ptr<mij::ProgFrame> prog;  // a progressive frame's scans (MIJ_ACCEPT_PROGRESSIVE); else null
   char err[200] = "";
   long long units() const {  // int16 coefficients == sample bytes of all padded planes
     long long u = 0;
@@ -714,30 +657,47 @@ struct Parsed {
 
 int be16(const uint8_t *p) { return (p[0] << 8) | p[1]; }
 
-int build_table(mij::DecTab &t, const uint8_t counts[16], const uint8_t *syms, int nsyms) {
-  memset(&t, 0, sizeof t);
-  memcpy(t.val, syms, nsyms);
-  int code = 0, k = 0;
-  for (int l = 1; l <= 16; l++) {
-    const int c = counts[l - 1];
-    t.valoff[l] = k - code;
-    t.maxcode[l] = c ? code + c - 1 : -1;
-    for (int i = 0; i < c; i++, k++, code++) {
-      if (l <= mij::LOOK) {
-        const int sh = mij::LOOK - l;
-        for (int f = 0; f < (1 << sh); f++) t.look[(code << sh) | f] = (uint16_t)((l << 8) | syms[k]);
-      }
+using mij::build_table;  // mij_huff.h
+
+int parse_progressive(const uint8_t *s, size_t n, Parsed &P, int frame);
+
+// The stream's frame header, found by walking the segments in front of the
+// first SOS (no rule of either stream kind is applied on the way): the SOFn
+// marker's second byte and, if the segment is long enough, width and height;
+// 0 if there is none.
+int frame_header(const uint8_t *s, size_t n, int *w, int *h) {
+  if (n < 4 || s[0] != 0xFF || s[1] != 0xD8) return 0;
+  size_t i = 2;
+  while (i + 4 <= n && s[i] == 0xFF) {
+    const int m = s[i + 1];
+    if (m == 0xFF) {
+      i++;
+      continue;
     }
-    if (code > (1 << l)) return -1;  // over-subscribed
-    code <<= 1;
+    if (m == 0xD9 || m == 0xDA || (m >= 0xD0 && m <= 0xD7)) break;
+    const size_t len = (size_t)((s[i + 2] << 8) | s[i + 3]);
+    if (len < 2 || i + 2 + len > n) break;
+    if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
+      if (len >= 7) {
+        if (h) *h = (s[i + 5] << 8) | s[i + 6];
+        if (w) *w = (s[i + 7] << 8) | s[i + 8];
+      }
+      return m;
+    }
+    i += 2 + len;
   }
-  t.maxcode[17] = 0x7fffffff;
   return 0;
 }
 
 // Host only (no device use): the message goes to P.err, since streams are
-// parsed on worker threads; the caller reports it.
-int parse(const uint8_t *s, size_t n, Parsed &P, int frame) {
+// parsed on worker threads; the caller reports it.  accept: MIJ_ACCEPT_*;
+// with 0 (the one-shot calls, a decoder by default) SOF2 is refused below.
+// With MIJ_ACCEPT_PROGRESSIVE the frame type is found first, so that the
+// segments in front of an SOF2 (a DHT with Th 2 or 3, say) are judged by the
+// progressive rules from the start, never by the baseline ones.
+int parse(const uint8_t *s, size_t n, Parsed &P, int frame, unsigned accept = 0) {
+  if ((accept & MIJ_ACCEPT_PROGRESSIVE) && frame_header(s, n, nullptr, nullptr) == 0xC2)
+    return parse_progressive(s, n, P, frame);
 #define BAD(...)                                  \
   do {                                            \
     snprintf(P.err, sizeof P.err, __VA_ARGS__);   \
@@ -937,6 +897,32 @@ int parse(const uint8_t *s, size_t n, Parsed &P, int frame) {
 #undef BAD
 }
 
+// A progressive stream (mij_progressive.h parses it and checks its scan
+// script): afterwards P describes the frame as everything downstream of the
+// entropy decoder expects an interleaved baseline frame without restart
+// intervals, which is what the progressive kernels leave in the arena.
+int parse_progressive(const uint8_t *s, size_t n, Parsed &P, int frame) {
+  P = Parsed();
+  auto F = std::make_shared<mij::ProgFrame>();
+  if (int rc = mij::prog_parse(s, n, *F, frame)) {
+    memcpy(P.err, F->err, sizeof P.err);
+    return rc;
+  }
+  P.w = F->w, P.h = F->h, P.ncomp = F->ncomp;
+  P.hmax = F->hmax, P.vmax = F->vmax, P.mcus_x = F->mcus_x, P.mcus_y = F->mcus_y;
+  for (int c = 0; c < 3; c++) {
+    P.cid[c] = F->cid[c], P.hs[c] = F->hs[c], P.vs[c] = F->vs[c], P.tq[c] = F->tq[c];
+    P.decl_hv[c] = F->decl_hv[c], P.bw[c] = F->bw[c], P.bh[c] = F->bh[c];
+  }
+  P.adobe = F->adobe;
+  memcpy(P.dqt, F->dqt, sizeof P.dqt);
+  memcpy(P.have_dqt, F->have_dqt, sizeof P.have_dqt);
+  P.interleaved = true;
+  P.ri = 0;
+  P.prog = F;
+  return MIJ_OK;
+}
+
 // where a frame of the last decode lives
 struct FrameLoc {
   long long off[3] = {0, 0, 0};  // first int16 / sample byte of each component's plane
@@ -984,6 +970,9 @@ struct mij_decoder {
   long long *d_entry = nullptr, *d_exit[2] = {nullptr, nullptr}, *d_base = nullptr;
   int *d_nblk = nullptr;
   int chunk_cap = 0, last_passes = 0;
+  unsigned accept = 0;        // MIJ_ACCEPT_* (mij_decoder_accept)
+  mij::ProgBuffers prog;      // the progressive path's buffers, allocated at its first use
+  int prog_mapping = mij::PROG_MAP_WAVE;  // the faster of the two as measured
   std::vector<Parsed> parsed;
   std::vector<FrameLoc> loc;
   int n = 0;
@@ -1072,6 +1061,7 @@ static void decoder_free(mij_decoder *d) {
                   (void *)d->t_err, (void *)d->t_out, (void *)d->t_len, (void *)d->x_plane, (void *)d->x_abs,
                   (void *)d->x_frames})
     hipFree(p);
+  mij::prog_free(d->prog);
   for (hipEvent_t e : d->rec_ev)
     if (e) hipEventDestroy(e);
   for (hipEvent_t e : d->tc_ev)
@@ -1255,6 +1245,76 @@ static int decode_scans(mij_decoder *d, std::vector<mij::DecIvl> &jobs, std::vec
   return MIJ_OK;
 }
 
+// The progressive frames of the call: their planes zeroed,
+// their units sorted by level and, inside a level, by scan, frame and
+// interval, one launch per level (mij_progressive.hip), then the hand-over.
+// piece0[f]: the first piece of frame f; at_len: every piece's blob offset
+// and unstuffed length; a frame's pieces are its scans' intervals in order.
+static int decode_progressive(mij_decoder *d, const std::vector<size_t> &piece0,
+                              const std::vector<std::pair<long long, long long>> &at_len, long long arena_units) {
+  const int n = (int)d->parsed.size();
+  std::vector<mij::DecTab> tabs;
+  std::vector<mij::ProgScanDev> scans;
+  std::vector<mij::ProgUnit> units;
+  std::vector<mij::ProgDcJob> dcjobs;
+  struct Key {
+    int level, ordinal, frame, ivl;
+  };
+  std::vector<Key> keys;
+  std::vector<ScanId> ids;
+  for (int f = 0; f < n; f++) {
+    const Parsed &P = d->parsed[f];
+    if (!P.prog) continue;
+    const mij::ProgFrame &F = *P.prog;
+    const FrameLoc &L = d->loc[f];
+    HIP_TRY(hipMemsetAsync(d->d_coef + L.off[0], 0, (size_t)P.units() * sizeof(int16_t), d->stream));
+    std::vector<size_t> first(F.scans.size() + 1, 0);  // of each scan's pieces, relative to the frame's
+    for (size_t k = 0; k < F.scans.size(); k++) first[k + 1] = first[k] + F.scans[k].ivl.size();
+    const size_t s0 = scans.size(), u0 = units.size();
+    const int tab0 = (int)tabs.size();
+    tabs.insert(tabs.end(), F.tabs.begin(), F.tabs.end());
+    auto piece = [&](int k, int i, long long &at, long long &len) {
+      const auto &pl = at_len[piece0[f] + first[k] + i];
+      at = pl.first, len = pl.second;
+    };
+    if (mij::prog_tables(F, L.off, tab0, piece, scans, units))
+      return mij_fail(MIJ_EJPEG, "stream %d: a restart interval has no MCUs", f);
+    for (size_t k = 0; k < F.scans.size(); k++) ids.push_back({f, (int)k});
+    for (size_t u = u0; u < units.size(); u++) {
+      const int k = units[u].scan - (int)s0;
+      keys.push_back({F.scans[k].level, k, f, (int)(u - u0 - first[k])});
+    }
+    for (int c = 0; c < P.ncomp; c++)
+      dcjobs.push_back({L.off[c], P.bw[c] * P.bh[c], P.bw[c], P.hs[c], P.vs[c], P.mcus_x, 0});
+  }
+  if (units.empty()) return MIJ_OK;
+  std::vector<int> order(units.size());
+  for (size_t i = 0; i < order.size(); i++) order[i] = (int)i;
+  std::sort(order.begin(), order.end(), [&](int a, int b) {
+    const Key &x = keys[a], &y = keys[b];
+    if (x.level != y.level) return x.level < y.level;
+    if (x.ordinal != y.ordinal) return x.ordinal < y.ordinal;
+    if (x.frame != y.frame) return x.frame < y.frame;
+    return x.ivl < y.ivl;
+  });
+  std::vector<mij::ProgUnit> sorted(units.size());
+  std::vector<int> level_end;
+  for (size_t i = 0; i < order.size(); i++) {
+    sorted[i] = units[order[i]];
+    const int lv = keys[order[i]].level;
+    if ((int)level_end.size() < lv) level_end.resize(lv, (int)i);
+    level_end[lv - 1] = (int)i + 1;
+  }
+  std::vector<int> st;
+  if (int rc = mij::prog_run(d->stream, d->prog, d->d_blob, d->d_coef, arena_units / 64, tabs, scans, sorted, level_end,
+                             dcjobs, d->prog_mapping, st))
+    return rc;
+  for (size_t s = 0; s < st.size(); s++)
+    if (st[s])
+      return mij_fail(MIJ_EJPEG, "stream %d scan %d: corrupt entropy data (%d)", ids[s].stream, ids[s].scan, st[s]);
+  return MIJ_OK;
+}
+
 // Parses n streams, stages their unstuffed scans and restart intervals in
 // one device blob and decodes them chunk-parallel.  Synchronous; the
 // coefficients stay on the device (mij_decoder_coefs / _component).
@@ -1281,7 +1341,8 @@ extern "C" int mij_decoder_decode(mij_decoder *d, const uint8_t *const *jpgs, co
   std::vector<int> prc(n, MIJ_OK);
   for (int f = 0; f < n; f++)
     if (!jpgs[f]) return mij_fail(MIJ_EINVAL, "decoder_decode: stream %d is NULL", f);
-  parallel([&](int f) { prc[f] = parse(jpgs[f], lens[f], d->parsed[f], f); });
+  const unsigned accept = d->accept;
+  parallel([&](int f) { prc[f] = parse(jpgs[f], lens[f], d->parsed[f], f, accept); });
   for (int f = 0; f < n; f++) {
     if (prc[f]) return mij_fail(prc[f], "decoder_decode: %s", d->parsed[f].err);
     const Parsed &P = d->parsed[f];
@@ -1306,7 +1367,10 @@ extern "C" int mij_decoder_decode(mij_decoder *d, const uint8_t *const *jpgs, co
       pieces.push_back({off, next, b, e, 0});
       off = next;
     };
-    if (P.interleaved)
+    if (P.prog)
+      for (const auto &sc : P.prog->scans)
+        for (const auto &iv : sc.ivl) add(iv.data, iv.end);
+    else if (P.interleaved)
       for (const auto &iv : P.ivl) add(iv.data, iv.end);
     else
       for (int k = 0; k < 3; k++) add(P.scan[k].data, P.scan[k].end);
@@ -1346,6 +1410,7 @@ extern "C" int mij_decoder_decode(mij_decoder *d, const uint8_t *const *jpgs, co
   std::vector<ScanId> ids;
   for (int f = 0; f < n; f++) {
     const Parsed &P = d->parsed[f];
+    if (P.prog) continue;  // decode_progressive below
     const int nscans = P.interleaved ? 1 : 3;
     for (int k = 0; k < nscans; k++) {
       mij::DecScan S;
@@ -1396,12 +1461,45 @@ extern "C" int mij_decoder_decode(mij_decoder *d, const uint8_t *const *jpgs, co
   HIP_TRY(hipMemcpyAsync(d->d_blob, d->h_blob, off, hipMemcpyHostToDevice, d->stream));
   HIP_TRY(hipMemcpyAsync(d->d_tabs, tabs.data(), tabs.size() * sizeof(mij::DecTab), hipMemcpyHostToDevice,
                          d->stream));
-  if (int rc = decode_scans(d, jobs, scans, ids)) return rc;
+  d->last_passes = 0;  // counts self-synchronising passes only
+  if (!scans.empty())
+    if (int rc = decode_scans(d, jobs, scans, ids)) return rc;
+  std::vector<std::pair<long long, long long>> at_len(pieces.size());
+  for (size_t p = 0; p < pieces.size(); p++) at_len[p] = {(long long)pieces[p].at, (long long)pieces[p].len};
+  if (int rc = decode_progressive(d, piece0, at_len, units)) return rc;
   d->n = n;
   return MIJ_OK;
 }
 
 extern "C" int mij_decoder_passes(mij_decoder *d) { return d ? d->last_passes : -1; }
+
+extern "C" int mij_decoder_accept(mij_decoder *d, unsigned mask) {
+  mij_clear_error();
+  if (!d) return mij_fail(MIJ_EINVAL, "decoder_accept: null decoder");
+  if (mask & ~(unsigned)MIJ_ACCEPT_PROGRESSIVE) return mij_fail(MIJ_EINVAL, "decoder_accept: unknown bits in mask 0x%X", mask);
+  d->accept = mask;
+  return MIJ_OK;
+}
+
+unsigned mij_decoder_accepted(mij_decoder *d) { return d ? d->accept : 0; }
+
+extern "C" int mij_decoder_scan_info(mij_decoder *d, int frame, int *progressive, int *nscans, int *levels) {
+  mij_clear_error();
+  if (!d || frame < 0 || frame >= d->n) return mij_fail(MIJ_EINVAL, "decoder_scan_info: bad frame");
+  const Parsed &P = d->parsed[frame];
+  if (progressive) *progressive = P.prog ? 1 : 0;
+  if (nscans) *nscans = P.prog ? (int)P.prog->scans.size() : P.interleaved ? 1 : 3;
+  if (levels) *levels = P.prog ? P.prog->levels : 1;
+  return MIJ_OK;
+}
+
+// test-only (mij_testing.h): the lane mapping of k_prog_scan, MIJ_PROG_MAP_*; returns the previous one
+extern "C" int mij_test_prog_mapping(mij_decoder *d, int mapping) {
+  if (!d || (mapping != mij::PROG_MAP_LANE && mapping != mij::PROG_MAP_WAVE)) return -2;
+  const int was = d->prog_mapping;
+  d->prog_mapping = mapping;
+  return was;
+}
 
 extern "C" int mij_decoder_info(mij_decoder *d, int frame, int *w, int *h, uint8_t dqt[128]) {
   mij_clear_error();
@@ -2158,8 +2256,20 @@ extern "C" void *mij_decoder_stream(mij_decoder *d) { return d ? (void *)d->stre
 
 // for the other host translation units (mij_host.h): the headers alone
 int mij_parse_size(const char *what, const uint8_t *jpg, size_t len, int frame, int *w, int *h) {
+  return mij_parse_size_accept(what, jpg, len, frame, 0, w, h);
+}
+
+extern "C" int mij_jpeg_size(const uint8_t *jpg, size_t len, int *w, int *h) {
+  int fw = 0, fh = 0;
+  if (!jpg || !frame_header(jpg, len, &fw, &fh)) return 0;
+  if (w) *w = fw;
+  if (h) *h = fh;
+  return 1;
+}
+
+int mij_parse_size_accept(const char *what, const uint8_t *jpg, size_t len, int frame, unsigned accept, int *w, int *h) {
   Parsed P;
-  if (int rc = parse(jpg, len, P, frame)) return mij_fail(rc, "%s: %s", what, P.err);
+  if (int rc = parse(jpg, len, P, frame, accept)) return mij_fail(rc, "%s: %s", what, P.err);
   *w = P.w;
   *h = P.h;
   return MIJ_OK;

@@ -25,6 +25,9 @@ int mij_batch_output_async(mij_batch *b, int frame, uint8_t *dst, size_t n);
 // the size in a stream's headers, parsed as mij_decoder_decode parses stream `frame` of a call: no device
 // work; what the decoder refuses is refused here, with its code and message (mij_decode.hip)
 int mij_parse_size(const char *what, const uint8_t *jpg, size_t len, int frame, int *w, int *h);
+// the same under an accept mask (MIJ_ACCEPT_*, mij_decoder_accept), and a decoder's mask
+int mij_parse_size_accept(const char *what, const uint8_t *jpg, size_t len, int frame, unsigned accept, int *w, int *h);
+unsigned mij_decoder_accepted(mij_decoder *d);
 
 // drop-in state shared with the detector's drop-in calls (mij_detect.hip)
 int mij_drop_stride();   // define.h:3 WIDTH, as set by mij_set_input_stride

@@ -454,6 +454,12 @@ extern "C" void mij_loader_destroy(mij_loader *l) { loader_free(l); }
 
 extern "C" void *mij_loader_stream(mij_loader *l) { return l ? mij_decoder_stream(l->d) : nullptr; }
 
+extern "C" int mij_loader_accept(mij_loader *l, unsigned mask) {
+  mij_clear_error();
+  if (!l) return mij_fail(MIJ_EINVAL, "loader_accept: null loader");
+  return mij_decoder_accept(l->d, mask);
+}
+
 extern "C" int mij_loader_denom(mij_loader *l) { return l && l->valid ? l->denom : 0; }
 
 extern "C" int mij_loader_load(mij_loader *l, const uint8_t *const *jpgs, const size_t *lens, int n, const area_t *crops,
@@ -481,7 +487,7 @@ extern "C" int mij_loader_load(mij_loader *l, const uint8_t *const *jpgs, const 
     if (!jpgs[i]) return mij_fail(MIJ_EINVAL, "%s: frame %d: stream is NULL", what, i);
     // the headers: what mij_decode refuses is refused here, with its code and message
     int w = 0, h = 0;
-    if (int rc = mij_parse_size(what, jpgs[i], lens[i], i, &w, &h)) return rc;
+    if (int rc = mij_parse_size_accept(what, jpgs[i], lens[i], i, l ? mij_decoder_accepted(l->d) : 0, &w, &h)) return rc;
     if (l && (w > l->max_w || h > l->max_h))
       return mij_fail(MIJ_EINVAL, "%s: frame %d: %dx%d exceeds the loader's %dx%d", what, i, w, h, l->max_w, l->max_h);
     area_t a = {0, 0, w, h};

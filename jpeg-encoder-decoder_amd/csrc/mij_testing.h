@@ -54,6 +54,12 @@ int mij_test_last_plan(mij_batch *b, int *out, int n);
  * fail alone with MIJ_ENOSPC.  Consumed by that encode.  Host state only.
  * Returns 0, or -2 on bad arguments. */
 int mij_test_sampled_out_cap(mij_batch *b, int frame, long long cap);
+/* The lane mapping of the progressive decoder's k_prog_scan:
+ * 0 = one unit (restart interval of a scan) per lane; 1 = one unit per wave,
+ * the default.  Both give the same planes; scripts/bench_progressive.py
+ * times them.  Returns the previous mapping, or -2 on bad arguments. */
+int mij_test_prog_mapping(mij_decoder *d, int mapping);
+
 #ifdef __cplusplus
 }
 #endif

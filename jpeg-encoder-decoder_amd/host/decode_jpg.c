@@ -11,7 +11,11 @@
  * With -scale 1/2, 1/4 or 1/8 the image comes out at that scale through
  * mij_decode_scaled, as djpeg -scale gives it (libjpeg's reduced IDCTs).
  *
- *   decode_jpg [-scale 1/N] <in.jpg> <out.ppm>
+ * With --progressive (first) progressive files are decoded too, through a
+ * decoder object with MIJ_ACCEPT_PROGRESSIVE set (the one-shot calls refuse
+ * them).
+ *
+ *   decode_jpg [--progressive] [-scale 1/N] <in.jpg> <out.ppm>
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -38,8 +42,13 @@ static uint8_t *read_file(const char *path, size_t *len) {
 }
 
 int main(int argc, char **argv) {
-    int denom = 1;
+    int denom = 1, progressive = 0;
     const char *prog = argv[0];
+    if (argc > 1 && !strcmp(argv[1], "--progressive")) {
+        progressive = 1;
+        argv++;
+        argc--;
+    }
     if (argc == 5 && !strcmp(argv[1], "-scale")) {
         char tail = 0;
         if (sscanf(argv[2], "1/%d%c", &denom, &tail) != 1 || (denom != 1 && denom != 2 && denom != 4 && denom != 8)) {
@@ -50,7 +59,7 @@ int main(int argc, char **argv) {
         argc -= 2;
     }
     if (argc != 3) {
-        fprintf(stderr, "usage: %s [-scale 1/N] <in.jpg> <out.ppm>\n", prog);
+        fprintf(stderr, "usage: %s [--progressive] [-scale 1/N] <in.jpg> <out.ppm>\n", prog);
         return 2;
     }
     size_t len = 0;
@@ -60,6 +69,42 @@ int main(int argc, char **argv) {
      * that reports the size and MIJ_ENOSPC before any device work */
     int w = 0, h = 0;
     uint8_t probe;
+    if (progressive) {
+        int fw = 16, fh = 16;
+        mij_jpeg_size(jpg, len, &fw, &fh);
+        mij_decoder *d = mij_decoder_create(0, fw < 16 ? 16 : (fw + 15) / 16 * 16, fh < 16 ? 16 : (fh + 15) / 16 * 16, 1);
+        const uint8_t *streams[1] = {jpg};
+        int lay[3 + 5 * 3];
+        int prc = d ? mij_decoder_accept(d, MIJ_ACCEPT_PROGRESSIVE) : mij_last_error();
+        if (!prc) prc = mij_decoder_decode(d, streams, &len, 1);
+        if (!prc) prc = mij_decoder_reconstruct_scaled(d, MIJ_PIX_RGB, denom);
+        if (!prc) prc = mij_decoder_scaled_layout(d, 0, denom, lay, 3 + 5 * 3);
+        const size_t pcap = !prc ? (size_t)3 * lay[0] * lay[1] : 0;
+        uint8_t *ppx = !prc ? malloc(pcap) : NULL;
+        int bad = 0;
+        if (!prc && !ppx) {
+            fprintf(stderr, "out of memory\n");
+            bad = 1;
+        }
+        if (!prc && !bad) prc = mij_decoder_pixels(d, 0, ppx, pcap, 0);
+        if (prc) {
+            fprintf(stderr, "%s: %s: %s\n", argv[1], mij_strerror(prc), mij_last_message());
+            bad = 1;
+        }
+        if (!bad) {
+            FILE *pf = fopen(argv[2], "wb");
+            if (!pf || fprintf(pf, "P6\n%d %d\n255\n", lay[0], lay[1]) < 0 || fwrite(ppx, 1, pcap, pf) != pcap || fclose(pf)) {
+                perror(argv[2]);
+                bad = 1;
+            } else {
+                printf("%s: %dx%d -> %s\n", argv[1], lay[0], lay[1], argv[2]);
+            }
+        }
+        if (d) mij_decoder_destroy(d);
+        free(ppx);
+        free(jpg);
+        return bad;
+    }
     int rc = mij_decode_scaled(jpg, len, MIJ_PIX_RGB, denom, &probe, 0, &w, &h);
     if (rc != MIJ_ENOSPC) {
         fprintf(stderr, "%s: %s: %s\n", argv[1], mij_strerror(rc), mij_last_message());

@@ -16,6 +16,8 @@
  *   -auto             the operation that makes the file's EXIF orientation upright
  *   -crop WxH+X+Y     X and Y multiples of the MCU size
  *   -trim             cut a mirrored edge down to whole MCUs instead of refusing it
+ *   --progressive     also take progressive files (MIJ_ACCEPT_PROGRESSIVE):
+ *                     "progressive in, optimised baseline out"
  * restart_rows then counts MCU rows of the output.
  */
 #include <stdint.h>
@@ -48,18 +50,24 @@ static int fail(const char *what, int rc) {
 }
 
 static int usage(const char *prog) {
-    fprintf(stderr, "usage: %s [-flip h|v] [-rotate 90|180|270] [-transpose] [-transverse] [-auto] [-trim]\n"
+    fprintf(stderr, "usage: %s [--progressive] [-flip h|v] [-rotate 90|180|270] [-transpose] [-transverse] [-auto] [-trim]\n"
             "       [-crop WxH+X+Y] <in.jpg> <out.jpg> [restart_rows]\n", prog);
     return 2;
 }
 
 int main(int argc, char **argv) {
     const char *prog = argv[0];
-    int op = MIJ_XF_NONE, flags = 0, have_crop = 0, have_xf = 0, automatic = 0;
+    int op = MIJ_XF_NONE, flags = 0, have_crop = 0, have_xf = 0, automatic = 0, progressive = 0;
     area_t crop = {0, 0, 0, 0};
     while (argc > 1 && argv[1][0] == '-' && argv[1][1]) {
         const char *o = argv[1], *v = argc > 2 ? argv[2] : "";
         int used = 1;
+        if (!strcmp(o, "--progressive")) {
+            progressive = 1;
+            argc--;
+            argv++;
+            continue;
+        }
         if (!strcmp(o, "-flip") && (!strcmp(v, "h") || !strcmp(v, "v"))) {
             op = v[0] == 'h' ? MIJ_XF_FLIP_H : MIJ_XF_FLIP_V, used = 2;
         } else if (!strcmp(o, "-rotate") && (!strcmp(v, "90") || !strcmp(v, "180") || !strcmp(v, "270"))) {
@@ -91,10 +99,19 @@ int main(int argc, char **argv) {
      * before any device work */
     int w = 0, h = 0;
     uint8_t probe;
-    int rc = mij_decode(jpg, len, MIJ_PIX_RGB, &probe, 0, &w, &h);
-    if (rc != MIJ_ENOSPC) return fail(argv[1], rc);
+    int rc;
+    if (progressive) {  /* the one-shot calls refuse SOF2: the size from the frame header itself */
+        w = h = 16;
+        mij_jpeg_size(jpg, len, &w, &h);
+        if (w < 1) w = 1;
+        if (h < 1) h = 1;
+    } else {
+        rc = mij_decode(jpg, len, MIJ_PIX_RGB, &probe, 0, &w, &h);
+        if (rc != MIJ_ENOSPC) return fail(argv[1], rc);
+    }
     mij_decoder *d = mij_decoder_create(0, (w + 15) / 16 * 16, (h + 15) / 16 * 16, 1);
     if (!d) return fail("mij_decoder_create", mij_last_error());
+    if (progressive && (rc = mij_decoder_accept(d, MIJ_ACCEPT_PROGRESSIVE)) != MIJ_OK) return fail("mij_decoder_accept", rc);
     const uint8_t *streams[1] = {jpg};
     if ((rc = mij_decoder_decode(d, streams, &len, 1)) != MIJ_OK) return fail(argv[1], rc);
     rc = have_xf ? mij_decoder_transform(d, op, flags, have_crop ? &crop : NULL, restart_rows)

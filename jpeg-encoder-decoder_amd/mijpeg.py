@@ -37,6 +37,7 @@ EXPORTS = [
     "subsample", "store", "compare", "enlargeAdjust", "mij_set_frame_height",
     "mij_decoder_create", "mij_decoder_destroy", "mij_decoder_decode", "mij_decoder_info",
     "mij_decoder_coefs", "mij_decoder_device_coefs", "mij_decoder_passes",
+    "mij_decoder_accept", "mij_decoder_scan_info", "mij_loader_accept", "mij_jpeg_size",
     "mij_decoder_reconstruct", "mij_decoder_pixels", "mij_decoder_planes", "mij_decoder_device_pixels",
     "mij_decoder_reconstruct_ms", "mij_decoder_stream", "mij_decode",
     "mij_decoder_layout", "mij_decoder_component", "mij_decoder_plane",
@@ -317,6 +318,11 @@ def load() -> C.CDLL:
         lib.mij_loader_ms.argtypes = [p, p]
         lib.mij_loader_stream.restype = p
         lib.mij_loader_stream.argtypes = [p]
+        lib.mij_decoder_accept.argtypes = [p, C.c_uint]
+        lib.mij_decoder_scan_info.argtypes = [p, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
+        lib.mij_loader_accept.argtypes = [p, C.c_uint]
+        lib.mij_jpeg_size.argtypes = [p, sz, C.POINTER(i), C.POINTER(i)]
+        lib.mij_test_prog_mapping.argtypes = [p, i]
     except AttributeError:
         if not os.environ.get("MIJ_LIB"):  # older builds only in A/B timing runs
             raise
@@ -1100,10 +1106,41 @@ def _order(order: str) -> int:
     return PIXEL_ORDERS[order]
 
 
-def decode(jpg: bytes, order: str = "bgr", scale: int = 1) -> np.ndarray:
+ACCEPT_PROGRESSIVE = 1  # MIJ_ACCEPT_PROGRESSIVE
+
+
+def jpeg_size(jpg: bytes):
+    """mij_jpeg_size: (w, h) from the stream's frame header, of any SOFn; (0, 0) where it has none"""
+    buf = np.frombuffer(jpg, np.uint8)
+    w, h = C.c_int(0), C.c_int(0)
+    load().mij_jpeg_size(_ptr(buf), buf.size, C.byref(w), C.byref(h))
+    return w.value, h.value
+
+
+def _progressive_decoder(jpg: bytes) -> "Decoder":
+    """a decoder of the stream's size with MIJ_ACCEPT_PROGRESSIVE set, holding the decoded stream"""
+    w, h = jpeg_size(jpg)  # (0, 0): the decoder then says what is wrong
+    d = Decoder(max(16, (w + 15) // 16 * 16), max(16, (h + 15) // 16 * 16), 1, progressive=True)
+    try:
+        d.decode([jpg])
+    except Exception:
+        d.close()
+        raise
+    return d
+
+
+def decode(jpg: bytes, order: str = "bgr", scale: int = 1, progressive: bool = False) -> np.ndarray:
     """mij_decode: one baseline JFIF stream -> (h, w, 3) uint8 pixels, host to
     host; scale = 2, 4, 8: mij_decode_scaled, the image at 1/scale as
-    libjpeg's reduced IDCTs give it."""
+    libjpeg's reduced IDCTs give it.  progressive=True: through
+    a Decoder that also accepts progressive streams."""
+    if progressive:
+        d = _progressive_decoder(jpg)
+        try:
+            d.reconstruct(order, scale)
+            return d.pixels(0)
+        finally:
+            d.close()
     lib = load()
     buf = np.frombuffer(jpg, np.uint8)
     w, h = C.c_int(0), C.c_int(0)
@@ -1125,10 +1162,19 @@ def decode(jpg: bytes, order: str = "bgr", scale: int = 1) -> np.ndarray:
     return out
 
 
-def transcode(jpg: bytes, restart_rows: int = 0) -> bytes:
+def transcode(jpg: bytes, restart_rows: int = 0, progressive: bool = False) -> bytes:
     """mij_transcode: one baseline stream -> the same coefficients in one
     interleaved scan with optimised Huffman tables and restart intervals of
-    restart_rows MCU rows (0: none), host to host; lossless"""
+    restart_rows MCU rows (0: none), host to host; lossless.
+    progressive=True: through a Decoder that also accepts progressive streams
+    ("progressive in, optimised baseline out")."""
+    if progressive:
+        d = _progressive_decoder(jpg)
+        try:
+            d.transcode(restart_rows)
+            return d.transcoded(0)
+        finally:
+            d.close()
     lib = load()
     buf = np.frombuffer(jpg, np.uint8)
     n = C.c_size_t(0)
@@ -1173,12 +1219,22 @@ def _xf_args(jpg, op, trim, crop):
     return int(op), XF_TRIM if trim is True else int(trim), area
 
 
-def transform(jpg: bytes, op="rot90", trim: bool = False, crop=None, restart_rows: int = 0) -> bytes:
+def transform(jpg: bytes, op="rot90", trim: bool = False, crop=None, restart_rows: int = 0,
+              progressive: bool = False) -> bytes:
     """mij_transform: one baseline stream -> the flipped / transposed / rotated
     (op, by name; "auto": by the stream's EXIF orientation) and / or cropped
     (crop = (x, y, w, h), MCU-aligned offset) image, coded as transcode codes
     it; lossless.  trim: cut a mirrored dimension down to
-    whole MCUs instead of refusing it."""
+    whole MCUs instead of refusing it.  progressive=True: through a Decoder
+    that also accepts progressive streams."""
+    if progressive:
+        code, _, _ = _xf_args(jpg, op, trim, crop)  # resolves "auto" from the stream
+        d = _progressive_decoder(jpg)
+        try:
+            d.transform(code, trim, crop, restart_rows)
+            return d.transcoded(0)
+        finally:
+            d.close()
     lib = load()
     buf = np.frombuffer(jpg, np.uint8)
     code, flags, area = _xf_args(jpg, op, trim, crop)
@@ -1196,15 +1252,28 @@ class Decoder:
     """Baseline JPEG streams (the encoder's own three-scan shape, and what
     libjpeg writes: one interleaved scan, greyscale / 4:4:4 / 4:2:2 / 4:2:0,
     any size, restart intervals) -> coefficient planes, entropy-decoded on
-    the GPU, and from those (reconstruct) the pixels libjpeg would give."""
+    the GPU, and from those (reconstruct) the pixels libjpeg would give.
+    progressive=True (mij_decoder_accept): progressive streams too."""
 
-    def __init__(self, max_w: int, max_h: int, max_frames: int, device: int = 0):
+    def __init__(self, max_w: int, max_h: int, max_frames: int, device: int = 0, progressive: bool = False):
         self.lib = load()
         self.scale_ = 1  # of the last reconstruct
         self.h_ = self.lib.mij_decoder_create(device, max_w, max_h, max_frames)
         if not self.h_:
             raise MijError("mij_decoder_create failed: "
                            f"{self.lib.mij_strerror(self.lib.mij_last_error()).decode()}")
+        if progressive:
+            self.accept(ACCEPT_PROGRESSIVE)
+
+    def accept(self, mask: int) -> None:
+        """mij_decoder_accept: what the decoder takes beyond baseline (ACCEPT_PROGRESSIVE), until changed"""
+        _check(self.lib.mij_decoder_accept(self.h_, mask), "decoder_accept")
+
+    def scan_info(self, frame: int) -> dict:
+        """mij_decoder_scan_info of the last decode: progressive (bool), nscans, levels"""
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        _check(self.lib.mij_decoder_scan_info(self.h_, frame, C.byref(a), C.byref(b), C.byref(c)), "decoder_scan_info")
+        return {"progressive": bool(a.value), "nscans": b.value, "levels": c.value}
 
     def close(self) -> None:
         if self.h_:
@@ -1661,7 +1730,7 @@ class Loader:
     """Stored JPEGs -> one normalised tensor on the device (mij_loader_*):
     decode at a scale, crop, resize, tensorize, on one stream."""
 
-    def __init__(self, max_w: int, max_h: int, max_frames: int, device: int = 0):
+    def __init__(self, max_w: int, max_h: int, max_frames: int, device: int = 0, progressive: bool = False):
         self.lib = load()
         self.last_ = None
         self.h_ = self.lib.mij_loader_create(device, max_w, max_h, max_frames)
@@ -1669,6 +1738,12 @@ class Loader:
             raise MijError("mij_loader_create failed: "
                            f"{self.lib.mij_strerror(self.lib.mij_last_error()).decode()}: "
                            f"{self.lib.mij_last_message().decode(errors='replace')}")
+        if progressive:
+            self.accept(ACCEPT_PROGRESSIVE)
+
+    def accept(self, mask: int) -> None:
+        """mij_loader_accept: as Decoder.accept, for the loader's decoder"""
+        _check(self.lib.mij_loader_accept(self.h_, mask), "loader_accept")
 
     def close(self) -> None:
         if self.h_:
