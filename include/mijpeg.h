@@ -990,6 +990,37 @@ int mij_exif_orientation(const uint8_t *jpg, size_t len);   /* 1..8; 1 when ther
  * anything outside 1..8) */
 int mij_orientation_op(int orientation);                    /* the op that makes it upright */
 
+/* ---- progressive output ----------------------------------------
+ * What jpegtran -progressive does: mij_decoder_transcode and
+ * mij_decoder_transform write every frame as a progressive file (SOF2)
+ * instead of one baseline scan.  Sticky like mij_decoder_accept; the default
+ * is MIJ_OUT_BASELINE, under which both calls write the bytes described
+ * above.  The same
+ * coefficients, sampling, size, component ids and DQT bytes as the baseline
+ * output; the scans are libjpeg's jpeg_simple_progression (ten for YCbCr:
+ * DC with Al 1, Y 1-5 Al 2, Cr and Cb 1-63 Al 1, Y 6-63 Al 2, Y refined to
+ * Al 1, DC refined, Cr, Cb, Y refined to Al 0; the six of component 0 for
+ * greyscale), coded by the rules of libjpeg's jcphuff.c with one optimised
+ * Huffman table per scan and component group, written in front of its scan
+ * (DC ids 0 / 1, AC ids 0 / 1 for component 0 / the others).  A scan of one
+ * component covers the blocks of that component's own ceil(w_c / 8) x
+ * ceil(h_c / 8) grid, so AC coefficients of MCU-padding blocks outside it
+ * are not coded (jpegtran does the same; no pixel changes).  restart_rows = r
+ * gives every scan the interval r x (its own MCUs across), a DRI wherever
+ * that changes; MIJ_EINVAL before any device work when r < 0 or an interval
+ * of any scan of any frame exceeds 65535 (the message names the frame).  A
+ * frame for which any table cannot be built gets length 0 and MIJ_ETABLE;
+ * the others succeed.  mij_decoder_transcoded, _device_transcoded and
+ * _transcode_ms serve the result as before.  The tables are this library's,
+ * not libjpeg's: the bytes differ from jpegtran's, the decoded coefficients
+ * do not. */
+enum { MIJ_OUT_BASELINE = 0, MIJ_OUT_PROGRESSIVE = 1 };
+int mij_decoder_output(mij_decoder *d, int format);
+/* one call, host to host, as mij_transcode, from a baseline or a progressive
+ * stream to a progressive one; cap 0 asks for the size */
+int mij_transcode_progressive(const uint8_t *jpg, size_t len, int restart_rows, uint8_t *out, size_t cap,
+                              size_t *out_len);
+
 /* Drop-in entry points of include/brain.h:7-10, on frames of
  * mij_set_input_stride() x mij_set_frame_height() pixels (define.h:3-4,
  * 320x240 by default).  subsample writes the PPM copy to f when f is not

@@ -48,6 +48,7 @@
 #include "mij_pixels.h"
 #include "mij_progressive.h"
 #include "mij_transcode.h"
+#include "mij_progwrite.h"
 #include "mij_transform.h"
 
 #define HIP_TRY(x)                                                                 \
@@ -1040,6 +1041,23 @@ struct mij_decoder {
   mij::XfFrame *x_frames = nullptr;
   size_t x_plane_cap = 0, x_abs_cap = 0, x_frames_cap = 0;
   std::vector<mij::XfFrame> h_xframes;
+  // progressive output (mij_decoder_output): one entry per scan
+  // of every frame; the other per-scan arrays are the transcoder's, grown
+  int out_fmt = MIJ_OUT_BASELINE;
+  mij::TcFrame *p_segs = nullptr;
+  mij::PwScan *p_sc = nullptr;
+  mij::PwFrame *p_pf = nullptr;
+  mij::TcOut *p_souts = nullptr;
+  uint8_t *p_info = nullptr;
+  uint16_t *p_runlen = nullptr;
+  int *p_perr = nullptr, *p_serr = nullptr;
+  uint64_t *p_slen = nullptr;
+  size_t p_segs_cap = 0, p_sc_cap = 0, p_pf_cap = 0, p_souts_cap = 0, p_info_cap = 0, p_runlen_cap = 0, p_perr_cap = 0,
+         p_serr_cap = 0, p_slen_cap = 0;
+  std::vector<mij::TcFrame> h_psegs;  // kept: the uploads are asynchronous
+  std::vector<mij::PwScan> h_psc;
+  std::vector<mij::PwFrame> h_ppf;
+  std::vector<mij::TcOut> h_psouts;
   // what max_frames frames of max_w x max_h of the encoder's shape take: int16
   // coefficients == sample bytes, and components == scans
   size_t floor_units() const { return (size_t)cap * max_w * max_h * 3 / 2; }
@@ -1059,7 +1077,8 @@ static void decoder_free(mij_decoder *d) {
                   (void *)d->t_mcu_off, (void *)d->t_row_bits, (void *)d->t_row_pre, (void *)d->t_ival,
                   (void *)d->t_row_off, (void *)d->t_bits, (void *)d->t_raw, (void *)d->t_ffc, (void *)d->t_hdr,
                   (void *)d->t_err, (void *)d->t_out, (void *)d->t_len, (void *)d->x_plane, (void *)d->x_abs,
-                  (void *)d->x_frames})
+                  (void *)d->x_frames, (void *)d->p_segs, (void *)d->p_sc, (void *)d->p_pf, (void *)d->p_souts,
+                  (void *)d->p_info, (void *)d->p_runlen, (void *)d->p_perr, (void *)d->p_serr, (void *)d->p_slen})
     hipFree(p);
   mij::prog_free(d->prog);
   for (hipEvent_t e : d->rec_ev)
@@ -1912,6 +1931,236 @@ static int xf_plan(const Parsed &P, int op, int flags, const area_t *crop, int r
   return MIJ_OK;
 }
 
+// ---------------------------------------------------------------------------
+// progressive output: host side
+// ---------------------------------------------------------------------------
+// the scan's own MCU grid: the frame's for an interleaved scan, the blocks
+// that cover component c's own samples otherwise
+static void pw_grid(const Parsed &P, const XfPlan &X, int comps, int &ux, int &uy) {
+  if (P.ncomp == 1) comps = 1;  // (its DC scans too are scans of component 0 alone)
+  if (comps == 7) {
+    ux = X.mcus_x;
+    uy = X.mcus_y;
+    return;
+  }
+  const int c = comps == 1 ? 0 : comps == 2 ? 1 : 2;
+  int hmax = 1, vmax = 1;
+  for (int k = 0; k < P.ncomp; k++) {
+    hmax = std::max(hmax, X.hs[k]);
+    vmax = std::max(vmax, X.vs[k]);
+  }
+  const int wc = (int)(((long long)X.w * X.hs[c] + hmax - 1) / hmax), hc = (int)(((long long)X.h * X.vs[c] + vmax - 1) / vmax);
+  ux = (wc + 7) / 8;  // <= mcus_x * hs
+  uy = (hc + 7) / 8;
+}
+
+// restart_rows rows of every scan's own MCUs must fit a DRI: before any device work
+static int pw_check(const Parsed &P, const XfPlan &X, int restart_rows, const char *who, int frame) {
+  for (const mij::PwScript &K : mij::PW_SCRIPT) {
+    if (P.ncomp == 1 && !(K.comps & 1)) continue;
+    int ux, uy;
+    pw_grid(P, X, K.comps, ux, uy);
+    const long long ri = (long long)restart_rows * ux;
+    if (restart_rows < 0 || ri > 65535)
+      return mij_fail(MIJ_EINVAL, "%s: frame %d: restart interval of %d rows x %d MCUs = %lld MCUs in the scan Ss %d Se %d "
+                      "Ah %d Al %d (0..65535)", who, frame, restart_rows, ux, ri, K.ss, K.se, K.ah, K.al);
+  }
+  return MIJ_OK;
+}
+
+// tc_run's second half when the decoder writes progressive files: the planes
+// and absolute DCs the frames' TcFrames point at (d->h_tframes, uploaded to
+// d->t_frames) become the scans of mij::PW_SCRIPT.  Waits for the device
+// twice, as tc_run does.
+static int pw_run(mij_decoder *d, int restart_rows, const XfPlan *plans, const char *who) {
+  const int n = d->n;
+  d->h_psegs.clear();
+  d->h_psc.clear();
+  d->h_ppf.assign(n, mij::PwFrame());
+  long long b0 = 0, m0 = 0, r0 = 0;
+  int npf = 0, max_nblk = 0, max_rows = 0, max_nint = 0;
+  for (int f = 0; f < n; f++) {
+    const Parsed &P = d->parsed[f];
+    const XfPlan &X = plans[f];
+    const mij::TcFrame &F = d->h_tframes[f];
+    mij::PwFrame &Q = d->h_ppf[f];
+    memset(&Q, 0, sizeof Q);
+    Q.seg0 = (int)d->h_psegs.size();
+    Q.pf0 = npf;
+    int ntab = 0;
+    for (const mij::PwScript &K : mij::PW_SCRIPT) {
+      if (P.ncomp == 1 && !(K.comps & 1)) continue;
+      const bool il = P.ncomp > 1 && K.comps == 7;
+      mij::TcFrame G;
+      memset(&G, 0, sizeof G);
+      mij::PwScan S;
+      memset(&S, 0, sizeof S);
+      pw_grid(P, X, K.comps, G.mcus_x, G.mcus_y);
+      if (il) {
+        for (int c = 0; c < 3; c++) G.c[c] = F.c[c];
+        G.ncomp = F.ncomp;
+        G.bpm = F.bpm;
+      } else {
+        S.comp = P.ncomp == 1 || K.comps == 1 ? 0 : K.comps == 2 ? 1 : 2;
+        G.c[0] = F.c[S.comp];
+        G.c[0].hs = G.c[0].vs = 1;  // (bw stays the padded plane's stride)
+        G.ncomp = 1;
+        G.bpm = 1;
+      }
+      G.R = restart_rows > 0 && restart_rows < G.mcus_y ? restart_rows : G.mcus_y;
+      G.nint = (G.mcus_y + G.R - 1) / G.R;
+      G.ri = restart_rows * G.mcus_x;
+      G.nblk = G.mcus_x * G.mcus_y * G.bpm;
+      G.blk0 = b0;
+      G.mcu0 = (int)m0;
+      G.row0 = (int)r0;
+      G.rowp0 = (int)r0 + (int)d->h_psegs.size();
+      S.frame = f;
+      S.ss = K.ss;
+      S.se = K.se;
+      S.ah = K.ah;
+      S.al = K.al;
+      S.ncomp = il ? P.ncomp : 1;
+      S.ntab = K.ss == 0 ? (K.ah ? 0 : il ? 2 : 1) : 1;
+      for (int t = 0; t < S.ntab; t++) S.tab[t] = 4 * Q.pf0 + ntab++;
+      S.first = Q.nseg == 0;
+      b0 += G.nblk;
+      m0 += (long long)G.mcus_x * G.mcus_y;
+      r0 += G.mcus_y;
+      max_nblk = std::max(max_nblk, G.nblk);
+      max_rows = std::max(max_rows, G.mcus_y);
+      max_nint = std::max(max_nint, G.nint);
+      d->h_psegs.push_back(G);
+      d->h_psc.push_back(S);
+      Q.nseg++;
+    }
+    Q.ntab = ntab;
+    Q.npf = (ntab + 3) / 4;
+    npf += Q.npf;
+  }
+  const int nseg = (int)d->h_psegs.size();
+  if (b0 > 0x7fff0000LL || m0 + nseg > 0x7fff0000LL) return mij_fail(MIJ_EINVAL, "%s: too many blocks", who);
+#define PW_GROW(p, cnt)                                            \
+  if (int rc = grow(d->p, d->p##_cap, (size_t)(cnt))) return rc
+  PW_GROW(p_segs, nseg);
+  PW_GROW(p_sc, nseg);
+  PW_GROW(p_pf, n);
+  PW_GROW(p_souts, nseg);
+  PW_GROW(p_info, b0);
+  PW_GROW(p_runlen, b0);
+  PW_GROW(p_perr, npf);
+  PW_GROW(p_serr, nseg);
+  PW_GROW(p_slen, nseg);
+  PW_GROW(t_hist, (size_t)npf * 4 * 257);
+  PW_GROW(t_ehuf, (size_t)npf * 1024);
+  PW_GROW(t_hc, (size_t)npf * 4);
+  PW_GROW(t_blk_bits, b0);
+  PW_GROW(t_mcu_off, m0);
+  PW_GROW(t_row_bits, r0);
+  PW_GROW(t_row_pre, r0 + nseg);
+  PW_GROW(t_ival, r0 + nseg);
+  PW_GROW(t_row_off, r0 + nseg);
+  PW_GROW(t_bits, nseg);
+  PW_GROW(t_hdr, nseg);
+  HIP_TRY(hipMemcpyAsync(d->p_segs, d->h_psegs.data(), nseg * sizeof(mij::TcFrame), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->p_sc, d->h_psc.data(), nseg * sizeof(mij::PwScan), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->p_pf, d->h_ppf.data(), n * sizeof(mij::PwFrame), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemsetAsync(d->t_hist, 0, sizeof(uint32_t) * npf * 4 * 257, d->stream));
+  HIP_TRY(hipMemsetAsync(d->p_perr, 0, sizeof(int) * npf, d->stream));
+  HIP_TRY(hipMemsetAsync(d->p_serr, 0, sizeof(int) * nseg, d->stream));
+  mij::PwArgs a;
+  memset(&a, 0, sizeof a);
+  a.seg.fr = d->p_segs;
+  a.seg.o = d->p_souts;
+  a.seg.nframes = nseg;
+  a.seg.max_nblk = max_nblk;
+  a.seg.max_rows = max_rows;
+  a.seg.hist = d->t_hist;
+  a.seg.ehuf = d->t_ehuf;
+  a.seg.hc = d->t_hc;
+  a.seg.blk_bits = d->t_blk_bits;
+  a.seg.mcu_off = d->t_mcu_off;
+  a.seg.row_bits = d->t_row_bits;
+  a.seg.row_pre = d->t_row_pre;
+  a.seg.ival_off = d->t_ival;
+  a.seg.row_off = d->t_row_off;
+  a.seg.bits = d->t_bits;
+  a.seg.hdr = d->t_hdr;
+  a.seg.out_len = d->p_slen;
+  a.seg.err = d->p_serr;
+  a.sc = d->p_sc;
+  a.pf = d->p_pf;
+  a.fr = d->t_frames;
+  a.nframes = n;
+  a.max_nint = max_nint;
+  a.info = d->p_info;
+  a.runlen = d->p_runlen;
+  a.perr = d->p_perr;
+  a.ferr = d->t_err;
+  a.flen = d->t_len;
+  HIP_TRY(mij::launch_pw_count(a, d->stream));
+  mij::EntArgs e;  // k_tables_1w: one wave per table, four per pseudo-frame
+  memset(&e, 0, sizeof e);
+  e.nframes = npf;
+  e.hist = d->t_hist;
+  e.ehuf = d->t_ehuf;
+  e.hc = d->t_hc;
+  e.err = d->p_perr;
+  HIP_TRY(mij::launch_tables(e, d->stream));
+  HIP_TRY(mij::launch_pw_sizes(a, d->stream));
+  // the scans' bits size their words and chunks, and their sum the frame's
+  // output: the header bound + every entropy byte stuffed + markers + EOI
+  std::vector<unsigned long long> bits(nseg);
+  HIP_TRY(hipMemcpyAsync(bits.data(), d->t_bits, nseg * sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  d->h_psouts.assign(nseg, mij::TcOut());
+  d->h_touts.assign(n, mij::TcOut());
+  long long raw = 0, out = 0, chunks = 0, max_chunks = 0;
+  for (int f = 0; f < n; f++) {
+    mij::PwFrame &Q = d->h_ppf[f];
+    long long cap = mij::PW_HDR_MAX + 2;
+    for (int s = Q.seg0; s < Q.seg0 + Q.nseg; s++) {
+      mij::TcOut &O = d->h_psouts[s];
+      const long long nbytes = (long long)(bits[s] >> 3), nch = (nbytes + mij::TC_CH - 1) / mij::TC_CH;
+      O.raw0 = raw;
+      O.raw_words = round_to((long long)(bits[s] / 128 + 1) * 4, 64);
+      O.out0 = out;  // the frame's: k_pw_head gives each scan its offset (TcArgs::hdr)
+      O.chunk0 = chunks;
+      raw += O.raw_words;
+      chunks += nch;
+      max_chunks = std::max(max_chunks, nch);
+      cap += 2 * nbytes + 2LL * d->h_psegs[s].nint;
+    }
+    cap = round_to(cap, 256);
+    if (cap > 0x7fff0000LL) return mij_fail(MIJ_ENOSPC, "%s: frame %d: a stream of up to %lld bytes", who, f, cap);
+    for (int s = Q.seg0; s < Q.seg0 + Q.nseg; s++) d->h_psouts[s].out_cap = cap;
+    Q.out0 = out;
+    Q.out_cap = cap;
+    d->h_touts[f].out0 = out;
+    d->h_touts[f].out_cap = cap;
+    out += cap;
+  }
+  PW_GROW(t_raw, raw);
+  PW_GROW(t_out, out);
+  PW_GROW(t_ffc, chunks + 1);
+#undef PW_GROW
+  HIP_TRY(hipMemcpyAsync(d->p_souts, d->h_psouts.data(), nseg * sizeof(mij::TcOut), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->p_pf, d->h_ppf.data(), n * sizeof(mij::PwFrame), hipMemcpyHostToDevice, d->stream));
+  a.seg.max_chunks = (int)std::min<long long>(max_chunks, 1 << 20);
+  a.seg.raw = d->t_raw;
+  a.seg.ffc = d->t_ffc;
+  a.seg.out = d->t_out;
+  HIP_TRY(mij::launch_pw_write(a, d->stream));
+  HIP_TRY(hipEventRecord(d->tc_ev[1], d->stream));
+  d->tc_len.assign(n, 0);
+  d->tc_err.assign(n, 0);
+  HIP_TRY(hipMemcpyAsync(d->tc_len.data(), d->t_len, n * sizeof(uint64_t), hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipMemcpyAsync(d->tc_err.data(), d->t_err, n * sizeof(int), hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(hipStreamSynchronize(d->stream));
+  d->tc_valid = true;
+  return MIJ_OK;
+}
+
 // Every frame of the last decode -> one interleaved baseline stream with the
 // same coefficients, sampling and DQTs, tables optimised for it and restart
 // intervals of restart_rows MCU rows.  Waits for the device twice: once for
@@ -2105,6 +2354,7 @@ static int tc_run(mij_decoder *d, int restart_rows, const XfPlan *plans, bool xf
   HIP_TRY(hipGetLastError());
   HIP_TRY(mij::launch_tc_abs(d->t_dcjobs, ncomp, max_comp, d->stream));
   if (xform) HIP_TRY(mij::launch_xf_blocks(d->x_frames, n, max_nblk, d->stream));
+  if (d->out_fmt == MIJ_OUT_PROGRESSIVE) return pw_run(d, restart_rows, plans, who);
   mij::TcArgs a;
   memset(&a, 0, sizeof a);
   a.fr = d->t_frames;
@@ -2190,6 +2440,9 @@ extern "C" int mij_decoder_transcode(mij_decoder *d, int restart_rows) {
   for (int f = 0; f < n; f++)
     if (int rc = xf_plan(d->parsed[f], MIJ_XF_NONE, 0, nullptr, restart_rows, "decoder_transcode", f, plans[f]))
       return rc;
+  if (d->out_fmt == MIJ_OUT_PROGRESSIVE)
+    for (int f = 0; f < n; f++)
+      if (int rc = pw_check(d->parsed[f], plans[f], restart_rows, "decoder_transcode", f)) return rc;
   return tc_run(d, restart_rows, plans.data(), false, "decoder_transcode");
 }
 
@@ -2205,6 +2458,9 @@ extern "C" int mij_decoder_transform(mij_decoder *d, int op, int flags, const ar
   std::vector<XfPlan> plans(n);
   for (int f = 0; f < n; f++)
     if (int rc = xf_plan(d->parsed[f], op, flags, crop, restart_rows, "decoder_transform", f, plans[f])) return rc;
+  if (d->out_fmt == MIJ_OUT_PROGRESSIVE)
+    for (int f = 0; f < n; f++)
+      if (int rc = pw_check(d->parsed[f], plans[f], restart_rows, "decoder_transform", f)) return rc;
   return tc_run(d, restart_rows, plans.data(), op != MIJ_XF_NONE || crop, "decoder_transform");
 }
 
@@ -2332,6 +2588,37 @@ extern "C" int mij_transcode(const uint8_t *jpg, size_t len, int restart_rows, u
                     restart_rows, P.mcus_x);
   mij_decoder *d = mij_decoder_create(mij_drop_device(), (P.w + 15) / 16 * 16, (P.h + 15) / 16 * 16, 1);
   if (!d) return mij_last_error();
+  int rc = mij_decoder_decode(d, &jpg, &len, 1);
+  if (!rc) rc = mij_decoder_transcode(d, restart_rows);
+  if (!rc) rc = mij_decoder_transcoded(d, 0, out, cap, out_len);
+  decoder_free(d);  // (leaves the failure's message in place)
+  return rc;
+}
+
+// what mij_decoder_transcode and mij_decoder_transform write from now on
+extern "C" int mij_decoder_output(mij_decoder *d, int format) {
+  mij_clear_error();
+  if (!d) return mij_fail(MIJ_EINVAL, "decoder_output: null decoder");
+  if (format != MIJ_OUT_BASELINE && format != MIJ_OUT_PROGRESSIVE)
+    return mij_fail(MIJ_EINVAL, "decoder_output: unknown format %d", format);
+  d->out_fmt = format;
+  return MIJ_OK;
+}
+
+extern "C" int mij_transcode_progressive(const uint8_t *jpg, size_t len, int restart_rows, uint8_t *out, size_t cap,
+                                         size_t *out_len) {
+  mij_clear_error();
+  if (out_len) *out_len = 0;
+  if (!jpg || (!out && cap)) return mij_fail(MIJ_EINVAL, "mij_transcode_progressive: NULL buffer");
+  Parsed P;  // the size first: the decoder is made for it; and every refusal, before any device work
+  if (int rc = parse(jpg, len, P, 0, MIJ_ACCEPT_PROGRESSIVE)) return mij_fail(rc, "mij_transcode_progressive: %s", P.err);
+  XfPlan X;
+  if (int rc = xf_plan(P, MIJ_XF_NONE, 0, nullptr, restart_rows, "mij_transcode_progressive", 0, X)) return rc;
+  if (int rc = pw_check(P, X, restart_rows, "mij_transcode_progressive", 0)) return rc;
+  mij_decoder *d = mij_decoder_create(mij_drop_device(), (P.w + 15) / 16 * 16, (P.h + 15) / 16 * 16, 1);
+  if (!d) return mij_last_error();
+  d->accept = MIJ_ACCEPT_PROGRESSIVE;
+  d->out_fmt = MIJ_OUT_PROGRESSIVE;
   int rc = mij_decoder_decode(d, &jpg, &len, 1);
   if (!rc) rc = mij_decoder_transcode(d, restart_rows);
   if (!rc) rc = mij_decoder_transcoded(d, 0, out, cap, out_len);

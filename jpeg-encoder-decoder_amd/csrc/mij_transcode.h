@@ -91,6 +91,12 @@ hipError_t launch_tc_hist(const TcArgs &a, hipStream_t s);
 hipError_t launch_tc_sizes(const TcArgs &a, hipStream_t s);
 // after the read-back of TcArgs::bits: zero, pack, 0xFF counts, headers, stuffed write
 hipError_t launch_tc_write(const TcArgs &a, hipStream_t s);
+// the same stages one by one, for the scans of a progressive file (mij_progwrite.hip): k_tc_rows and k_tc_scan
+// over blk_bits; k_tc_zero; k_tc_ffcount; k_tc_write (it needs hdr, out_len and the exclusive ffc of a head stage)
+hipError_t launch_tc_layout(const TcArgs &a, hipStream_t s);
+hipError_t launch_tc_zero(const TcArgs &a, hipStream_t s);
+hipError_t launch_tc_ffcount(const TcArgs &a, hipStream_t s);
+hipError_t launch_tc_stuffed(const TcArgs &a, hipStream_t s);
 // k_tables_1w (mij_kernels.hip): reads hist, hc, ehuf, err, nframes
 hipError_t launch_tables(const EntArgs &a, hipStream_t s);
 

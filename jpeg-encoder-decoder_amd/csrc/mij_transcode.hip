@@ -494,4 +494,32 @@ hipError_t launch_tc_write(const TcArgs &a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// The stages a progressive file's scans share with the one-scan coder
+// (mij_progwrite.hip): each scan is a "frame" of TcArgs.
+hipError_t launch_tc_layout(const TcArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_tc_rows, dim3(a.max_rows, a.nframes), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_tc_scan, dim3(a.nframes), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+static dim3 tc_chunk_grid(const TcArgs &a) {
+  const int nch = a.max_chunks < 1 ? 1 : a.max_chunks;
+  return dim3((unsigned)(nch < 256 ? nch : 256), a.nframes);
+}
+
+hipError_t launch_tc_zero(const TcArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_tc_zero, dim3(64, a.nframes), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_tc_ffcount(const TcArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_tc_ffcount, tc_chunk_grid(a), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_tc_stuffed(const TcArgs &a, hipStream_t s) {
+  hipLaunchKernelGGL(k_tc_write, tc_chunk_grid(a), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 }  // namespace mij

@@ -18,6 +18,10 @@
  *   -trim             cut a mirrored edge down to whole MCUs instead of refusing it
  *   --progressive     also take progressive files (MIJ_ACCEPT_PROGRESSIVE):
  *                     "progressive in, optimised baseline out"
+ *   --write-progressive   write a progressive file (jpegtran -progressive,
+ *                     mij_decoder_output): libjpeg's ten-scan script, tables
+ *                     optimised per scan; restart_rows counts rows of each
+ *                     scan's own MCUs
  * restart_rows then counts MCU rows of the output.
  */
 #include <stdint.h>
@@ -50,20 +54,26 @@ static int fail(const char *what, int rc) {
 }
 
 static int usage(const char *prog) {
-    fprintf(stderr, "usage: %s [--progressive] [-flip h|v] [-rotate 90|180|270] [-transpose] [-transverse] [-auto] [-trim]\n"
+    fprintf(stderr, "usage: %s [--progressive] [--write-progressive] [-flip h|v] [-rotate 90|180|270] [-transpose] [-transverse] [-auto] [-trim]\n"
             "       [-crop WxH+X+Y] <in.jpg> <out.jpg> [restart_rows]\n", prog);
     return 2;
 }
 
 int main(int argc, char **argv) {
     const char *prog = argv[0];
-    int op = MIJ_XF_NONE, flags = 0, have_crop = 0, have_xf = 0, automatic = 0, progressive = 0;
+    int op = MIJ_XF_NONE, flags = 0, have_crop = 0, have_xf = 0, automatic = 0, progressive = 0, write_progressive = 0;
     area_t crop = {0, 0, 0, 0};
     while (argc > 1 && argv[1][0] == '-' && argv[1][1]) {
         const char *o = argv[1], *v = argc > 2 ? argv[2] : "";
         int used = 1;
         if (!strcmp(o, "--progressive")) {
             progressive = 1;
+            argc--;
+            argv++;
+            continue;
+        }
+        if (!strcmp(o, "--write-progressive")) {
+            write_progressive = 1;
             argc--;
             argv++;
             continue;
@@ -112,6 +122,7 @@ int main(int argc, char **argv) {
     mij_decoder *d = mij_decoder_create(0, (w + 15) / 16 * 16, (h + 15) / 16 * 16, 1);
     if (!d) return fail("mij_decoder_create", mij_last_error());
     if (progressive && (rc = mij_decoder_accept(d, MIJ_ACCEPT_PROGRESSIVE)) != MIJ_OK) return fail("mij_decoder_accept", rc);
+    if (write_progressive && (rc = mij_decoder_output(d, MIJ_OUT_PROGRESSIVE)) != MIJ_OK) return fail("mij_decoder_output", rc);
     const uint8_t *streams[1] = {jpg};
     if ((rc = mij_decoder_decode(d, streams, &len, 1)) != MIJ_OK) return fail(argv[1], rc);
     rc = have_xf ? mij_decoder_transform(d, op, flags, have_crop ? &crop : NULL, restart_rows)

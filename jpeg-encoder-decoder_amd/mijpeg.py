@@ -52,7 +52,7 @@ EXPORTS = [
     "mij_max_jpg_bytes_any", "mij_batch_pad_input", "mij_batch_upload_any", "mij_batch_encode_interleaved",
     "mij_encode_any",
     "mij_decoder_transcode", "mij_decoder_transcoded", "mij_decoder_device_transcoded", "mij_decoder_transcode_ms",
-    "mij_transcode",
+    "mij_transcode", "mij_decoder_output", "mij_transcode_progressive",
     "mij_decoder_transform", "mij_transform", "mij_exif_orientation", "mij_orientation_op",
     "mij_decoder_reconstruct_scaled", "mij_decoder_scaled_layout", "mij_decode_scaled",
     "mij_max_jpg_bytes_sampled", "mij_batch_encode_sampled", "mij_batch_sampled_component",
@@ -323,6 +323,8 @@ def load() -> C.CDLL:
         lib.mij_loader_accept.argtypes = [p, C.c_uint]
         lib.mij_jpeg_size.argtypes = [p, sz, C.POINTER(i), C.POINTER(i)]
         lib.mij_test_prog_mapping.argtypes = [p, i]
+        lib.mij_decoder_output.argtypes = [p, i]
+        lib.mij_transcode_progressive.argtypes = [p, sz, i, p, sz, C.POINTER(sz)]
     except AttributeError:
         if not os.environ.get("MIJ_LIB"):  # older builds only in A/B timing runs
             raise
@@ -1117,11 +1119,12 @@ def jpeg_size(jpg: bytes):
     return w.value, h.value
 
 
-def _progressive_decoder(jpg: bytes) -> "Decoder":
-    """a decoder of the stream's size with MIJ_ACCEPT_PROGRESSIVE set, holding the decoded stream"""
+def _progressive_decoder(jpg: bytes, progressive: bool = True, output: str = "baseline") -> "Decoder":
+    """a decoder of the stream's size with MIJ_ACCEPT_PROGRESSIVE set (or not), holding the decoded stream"""
     w, h = jpeg_size(jpg)  # (0, 0): the decoder then says what is wrong
-    d = Decoder(max(16, (w + 15) // 16 * 16), max(16, (h + 15) // 16 * 16), 1, progressive=True)
+    d = Decoder(max(16, (w + 15) // 16 * 16), max(16, (h + 15) // 16 * 16), 1, progressive=progressive)
     try:
+        d.output(output)
         d.decode([jpg])
     except Exception:
         d.close()
@@ -1162,14 +1165,19 @@ def decode(jpg: bytes, order: str = "bgr", scale: int = 1, progressive: bool = F
     return out
 
 
-def transcode(jpg: bytes, restart_rows: int = 0, progressive: bool = False) -> bytes:
+# mij_decoder_output (include/mijpeg.h: MIJ_OUT_*)
+OUTPUTS = {"baseline": 0, "progressive": 1}
+
+
+def transcode(jpg: bytes, restart_rows: int = 0, progressive: bool = False, output: str = "baseline") -> bytes:
     """mij_transcode: one baseline stream -> the same coefficients in one
     interleaved scan with optimised Huffman tables and restart intervals of
     restart_rows MCU rows (0: none), host to host; lossless.
     progressive=True: through a Decoder that also accepts progressive streams
-    ("progressive in, optimised baseline out")."""
-    if progressive:
-        d = _progressive_decoder(jpg)
+    ("progressive in, optimised baseline out").  output="progressive": the
+    same coefficients as a progressive file instead."""
+    if progressive or output != "baseline":
+        d = _progressive_decoder(jpg, progressive, output)
         try:
             d.transcode(restart_rows)
             return d.transcoded(0)
@@ -1220,16 +1228,17 @@ def _xf_args(jpg, op, trim, crop):
 
 
 def transform(jpg: bytes, op="rot90", trim: bool = False, crop=None, restart_rows: int = 0,
-              progressive: bool = False) -> bytes:
+              progressive: bool = False, output: str = "baseline") -> bytes:
     """mij_transform: one baseline stream -> the flipped / transposed / rotated
     (op, by name; "auto": by the stream's EXIF orientation) and / or cropped
     (crop = (x, y, w, h), MCU-aligned offset) image, coded as transcode codes
     it; lossless.  trim: cut a mirrored dimension down to
     whole MCUs instead of refusing it.  progressive=True: through a Decoder
-    that also accepts progressive streams."""
-    if progressive:
+    that also accepts progressive streams.  output="progressive": written
+    as a progressive file."""
+    if progressive or output != "baseline":
         code, _, _ = _xf_args(jpg, op, trim, crop)  # resolves "auto" from the stream
-        d = _progressive_decoder(jpg)
+        d = _progressive_decoder(jpg, progressive, output)
         try:
             d.transform(code, trim, crop, restart_rows)
             return d.transcoded(0)
@@ -1268,6 +1277,13 @@ class Decoder:
     def accept(self, mask: int) -> None:
         """mij_decoder_accept: what the decoder takes beyond baseline (ACCEPT_PROGRESSIVE), until changed"""
         _check(self.lib.mij_decoder_accept(self.h_, mask), "decoder_accept")
+
+    def output(self, fmt: str) -> None:
+        """mij_decoder_output: what transcode and transform write, "baseline" (the default) or "progressive",
+        until changed"""
+        if fmt not in OUTPUTS:
+            raise MijError(f"output {fmt!r}: one of {', '.join(OUTPUTS)}")
+        _check(self.lib.mij_decoder_output(self.h_, OUTPUTS[fmt]), "decoder_output")
 
     def scan_info(self, frame: int) -> dict:
         """mij_decoder_scan_info of the last decode: progressive (bool), nscans, levels"""
