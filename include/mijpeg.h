@@ -928,7 +928,19 @@ void *mij_loader_stream(mij_loader *l);
  * that never transcodes allocates none).  It neither needs nor disturbs
  * mij_decoder_reconstruct: both may follow one decode, in either order.  A
  * frame whose tables cannot be built (MIJ_ETABLE from the two calls below,
- * length 0) does not fail the others. */
+ * length 0) does not fail the others.
+ *
+ * DC range.  A block's absolute DC is the sum of its interval's coded
+ * differences modulo 2^16, as int16: what mij_decoder_component reports,
+ * what the pixels are made from and what is coded here.  A stream no 8-bit
+ * image gives can put neighbouring DCs of the new scan more than 32767
+ * apart; that difference is of category 16, which no JPEG can carry.  Such a
+ * frame is refused: MIJ_EJPEG from the two calls below, with a message naming
+ * the frame, length 0, nothing written; the other frames of the call are
+ * served.  So a stream this call returns always decodes, here and in
+ * libjpeg, to the source's coefficients.  (mij_transcode, one frame, fails
+ * as a whole.  Progressive output, MIJ_OUT_PROGRESSIVE, cannot meet the
+ * case: its first DC scan codes the DCs halved.) */
 int mij_decoder_transcode(mij_decoder *d, int restart_rows);
 /* host copy of frame's stream; *len (may be NULL) its size, also with
  * MIJ_ENOSPC (cap 0, dst NULL asks for it); waits.  MIJ_EINVAL before a

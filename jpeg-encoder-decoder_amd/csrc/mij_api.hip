@@ -94,6 +94,9 @@ int mij_frame_fail(int ferr, const char *what, int frame) {
                   "publication lost, or a stale pack ticket)", what, frame);
     case FERR_OVERFLOW: return fail(MIJ_ENOSPC, "%s %d: bits past the scan buffer", what, frame);
     case FERR_ASSEMBLY: return fail(MIJ_ENOSPC, "%s %d: a band piece outside its buffer", what, frame);
+    case FERR_DCRANGE:
+      return fail(MIJ_EJPEG, "%s %d: a DC difference of category 16 (neighbouring DCs more than 32767 apart in the "
+                  "new scan), which no JPEG can carry", what, frame);
   }
   return fail(MIJ_ETABLE, "%s %d: Huffman table construction failed", what, frame);
 }

@@ -462,9 +462,17 @@ __global__ __launch_bounds__(64) void k_dec_dcbase(const RecJob *jobs, int njobs
 // raster order (bw == mcus_x); without DC resets the segment begins at 0.
 // RASTER: the host found both true of every job of the launch (hs * vs == 1,
 // seg >= nblocks), so the rule is one prefix sum at blk < nblocks.
+//
+// DC range: the absolute DC is the sum of the coded
+// differences modulo 2^16, as int16 -- the value mij_decoder_component
+// reports and the transcoder codes (k_tc_abs) -- so the pixels are those of
+// the planes also where a stream's sums leave int16, which no 8-bit image's
+// do.  dc16 sign-extends the low half of the 32-bit sum.
+__device__ __forceinline__ uint32_t dc16(uint32_t v) { return (uint32_t)(int32_t)(int16_t)v; }
+
 template <bool RASTER>
 __device__ __forceinline__ uint32_t rec_dc(const RecJob &j, const int32_t *pd, const uint32_t *tile, int blk) {
-  if (RASTER) return (uint32_t)pd[blk] + tile[j.tile0 + blk / DC_TILE];
+  if (RASTER) return dc16((uint32_t)pd[blk] + tile[j.tile0 + blk / DC_TILE]);
   int s = blk;
   if (j.hs * j.vs > 1) {
     const int by = blk / j.bw, bx = blk - by * j.bw;
@@ -474,7 +482,7 @@ __device__ __forceinline__ uint32_t rec_dc(const RecJob &j, const int32_t *pd, c
   const int s0 = j.seg >= j.nblocks ? 0 : s / j.seg * j.seg;
   uint32_t v = (uint32_t)pd[s] + tile[j.tile0 + s / DC_TILE];
   if (s0 > 0) v -= (uint32_t)pd[s0 - 1] + tile[j.tile0 + (s0 - 1) / DC_TILE];
-  return v;
+  return dc16(v);
 }
 
 // A component whose blocks become S x S samples (8 at full size; at 1/2, 1/4

@@ -90,13 +90,16 @@ inline int build_table(DecTab &t, const uint8_t counts[16], const uint8_t *syms,
     const int c = counts[l - 1];
     t.valoff[l] = k - code;
     t.maxcode[l] = c ? code + c - 1 : -1;
+    // over-subscribed: refused before the lookahead is filled, whose index
+    // (code << sh) would otherwise leave the table (a DHT may claim 255
+    // codes of 1 bit)
+    if (code + c > (1 << l)) return -1;
     for (int i = 0; i < c; i++, k++, code++) {
       if (l <= LOOK) {
         const int sh = LOOK - l;
         for (int f = 0; f < (1 << sh); f++) t.look[(code << sh) | f] = (uint16_t)((l << 8) | syms[k]);
       }
     }
-    if (code > (1 << l)) return -1;  // over-subscribed
     code <<= 1;
   }
   t.maxcode[17] = 0x7fffffff;

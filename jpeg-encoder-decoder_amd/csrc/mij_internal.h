@@ -28,6 +28,7 @@ constexpr int FERR_ASSEMBLY = 3;  // band assembly: a piece outside its buffer
 // fault, armed only through mij_test_stale_ticket (csrc/mij_testing.h)
 constexpr int OPT_TEST_FAULT_TICKET = 7;
 constexpr int FERR_SPIN = 4;      // a device-side wait outlasted SPIN_TICKS, or a stale pack ticket
+constexpr int FERR_DCRANGE = 5;   // transcoding: a DC difference of category 16, which no JPEG can carry
 // bound of every device-side wait without progress (s_memrealtime ticks,
 // 100 MHz: 2 s); the waits are microseconds long when the state they wait on
 // is intact, and the bound is long enough for a queue switched out under

@@ -95,8 +95,15 @@ __global__ __launch_bounds__(256) void k_tc_hist(TcArgs a) {
   for (int i = threadIdx.x; i < 1024; i += 256) h[i >> 8][i & 255] = 0;
   __syncthreads();
   TcBlk b;
-  if (tc_thread_block(F, blockIdx.x * 256 + threadIdx.x, b))
+  if (tc_thread_block(F, blockIdx.x * 256 + threadIdx.x, b)) {
+    // Absolute DCs are int16, so a difference has category <= 16, and 16 has no
+    // code in any JPEG: the frame is refused, the later stages skip it and
+    // nothing of it is written (DESIGN.md §4h "DC range").  Every lane that
+    // finds one stores the same value; the symbol is still counted (16 < 256),
+    // so that the table builder sees counts it can serve and leaves the code.
+    if (il_class(b.diff) > 15) a.err[f] = FERR_DCRANGE;
     il_walk(b.coef, b.diff, [&](int ac, int sym, int, int) { atomicAdd(&h[b.t0 + ac][sym & 255], 1u); });
+  }
   __syncthreads();
   uint32_t *gh = a.hist + (long long)f * 4 * 257;
   for (int i = threadIdx.x; i < 1024; i += 256) {
