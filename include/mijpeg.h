@@ -642,8 +642,24 @@ void *mij_decoder_device_coefs(mij_decoder *d, int frame);
  * nothing differs from a library without it, SOF2 is refused as not
  * baseline.  Unknown bits: MIJ_EINVAL, the mask unchanged.  The one-shot
  * calls (mij_decode, mij_decode_scaled, mij_transcode, mij_transform,
- * mij_thumbnail*) always refuse SOF2. */
+ * mij_thumbnail*) always refuse SOF2.
+ *
+ * MIJ_ACCEPT_440: three-component streams with luma 1x2 and
+ * chroma 1x1 ("4:4:0": what jpegtran, a phone gallery or this library's own
+ * transforms make of a 4:2:2 file turned by a quarter), baseline, and
+ * progressive when MIJ_ACCEPT_PROGRESSIVE is set as well.  The MCU is 8 x 16,
+ * two luma blocks top then bottom; the chroma planes are w x ceil(h / 2) and
+ * are upsampled as libjpeg's h1v2_fancy_upsample does (at 1/8 scale each row
+ * twice), the pixels libjpeg's byte for byte at every scale.  Such a frame
+ * is served like any other: layout, component, reconstruct at every scale,
+ * transcode (SOF H/V bytes 0x12 0x11 0x11), transform, thumbnails, the loader.
+ * With the bit set a transposing operation of mij_decoder_transform on a
+ * frame whose H != V is planned with every component's H and V swapped
+ * (4:2:2 -> 4:4:0, 4:4:0 -> 4:2:2, as jpegtran does) instead of refused.
+ * With the bit clear nothing differs from a library without it; the one-shot
+ * calls always refuse luma 1x2 and that operation.  Bit value 2 is unknown. */
 #define MIJ_ACCEPT_PROGRESSIVE 1
+#define MIJ_ACCEPT_440 4
 int mij_decoder_accept(mij_decoder *d, unsigned mask);
 /* of stream `frame` of the last decode (any pointer may be NULL): 1 if it was
  * progressive; its scans (a baseline file: 1, the encoder's shape: 3); the
@@ -660,7 +676,8 @@ int mij_jpeg_size(const uint8_t *jpg, size_t len, int *w, int *h);
 /* ---- ordinary baseline files -------------------------------------------------
  * mij_decoder_decode also accepts what libjpeg, Pillow, cameras and browsers
  * write: 8-bit baseline (SOF0, Huffman), greyscale or YCbCr with luma 1x1
- * (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0) and chroma 1x1, any width and height
+ * (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0) -- with MIJ_ACCEPT_440 also 1x2
+ * (4:4:0) -- and chroma 1x1, any width and height
  * up to the decoder's, one interleaved scan, DQT ids 0..3, arbitrary
  * component ids, restart intervals.  Such a frame's planes are padded to
  * whole MCUs; mij_decoder_coefs / _planes are defined as the encoder's layout
@@ -979,7 +996,10 @@ int mij_transcode(const uint8_t *jpg, size_t len, int restart_rows, uint8_t *out
  * unknown op or flag bit; a crop that is misaligned, empty or outside the
  * frame; a mirrored dimension that is not whole MCUs without MIJ_XF_TRIM, or
  * of which nothing is left with it; a transposing operation on a frame with a
- * component whose H != V (4:2:2: the decoder would refuse the result); an
+ * component whose H != V (4:2:2, 4:4:0) unless the decoder has MIJ_ACCEPT_440
+ * set, with which it can read the result (H and V of every component swap:
+ * the trim and whole-MCU rules use the source's MCU, the output grid and
+ * restart_rows the output's); an
  * interval over 65535 MCUs of the output grid.  One refused frame refuses the
  * call.  MIJ_XF_NONE without a crop is mij_decoder_transcode, byte for byte.
  * The results are read with mij_decoder_transcoded, _device_transcoded and

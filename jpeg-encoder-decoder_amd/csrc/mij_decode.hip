@@ -21,7 +21,9 @@
 // missing tables, restart markers missing or out of order.  (c) Opt-in
 // (mij_decoder_accept): progressive streams, parsed by mij_progressive.h and
 // decoded by mij_progressive.hip into the same arena; this
-// file stages their scans and describes the result as a frame of shape (b).
+// file stages their scans and describes the result as a frame of shape (b);
+// and luma 1x2 (4:4:0, MIJ_ACCEPT_440), with which a
+// transposing transform of a frame with H != V swaps them.
 //
 // Host: marker parsing (SOI, APPn, DQT, DHT, DRI, SOF0, SOS, EOI), canonical
 // Huffman tables with a 9-bit lookahead, and the scans copied unstuffed
@@ -668,7 +670,7 @@ int be16(const uint8_t *p) { return (p[0] << 8) | p[1]; }
 
 using mij::build_table;  // mij_huff.h
 
-int parse_progressive(const uint8_t *s, size_t n, Parsed &P, int frame);
+int parse_progressive(const uint8_t *s, size_t n, Parsed &P, int frame, unsigned accept);
 
 // The stream's frame header, found by walking the segments in front of the
 // first SOS (no rule of either stream kind is applied on the way): the SOFn
@@ -700,13 +702,14 @@ int frame_header(const uint8_t *s, size_t n, int *w, int *h) {
 
 // Host only (no device use): the message goes to P.err, since streams are
 // parsed on worker threads; the caller reports it.  accept: MIJ_ACCEPT_*;
-// with 0 (the one-shot calls, a decoder by default) SOF2 is refused below.
+// with 0 (the one-shot calls, a decoder by default) SOF2 is refused below,
+// and luma 1x2 (4:4:0, MIJ_ACCEPT_440) by both parsers.
 // With MIJ_ACCEPT_PROGRESSIVE the frame type is found first, so that the
 // segments in front of an SOF2 (a DHT with Th 2 or 3, say) are judged by the
 // progressive rules from the start, never by the baseline ones.
 int parse(const uint8_t *s, size_t n, Parsed &P, int frame, unsigned accept = 0) {
   if ((accept & MIJ_ACCEPT_PROGRESSIVE) && frame_header(s, n, nullptr, nullptr) == 0xC2)
-    return parse_progressive(s, n, P, frame);
+    return parse_progressive(s, n, P, frame, accept);
 #define BAD(...)                                  \
   do {                                            \
     snprintf(P.err, sizeof P.err, __VA_ARGS__);   \
@@ -775,8 +778,11 @@ int parse(const uint8_t *s, size_t n, Parsed &P, int frame, unsigned accept = 0)
       } else {
         if (P.hs[1] != 1 || P.vs[1] != 1 || P.hs[2] != 1 || P.vs[2] != 1)
           BAD("stream %d: chroma sampling %dx%d / %dx%d (only 1x1)", frame, P.hs[1], P.vs[1], P.hs[2], P.vs[2]);
-        if (!(P.hs[0] <= 2 && P.vs[0] <= P.hs[0]))
+        if (!(P.hs[0] <= 2 && P.vs[0] <= P.hs[0]) && !((accept & MIJ_ACCEPT_440) && P.hs[0] == 1 && P.vs[0] == 2)) {
+          if (accept & MIJ_ACCEPT_440)
+            BAD("stream %d: luma sampling %dx%d (only 1x1, 2x1, 2x2, 1x2)", frame, P.hs[0], P.vs[0]);
           BAD("stream %d: luma sampling %dx%d (only 1x1, 2x1, 2x2)", frame, P.hs[0], P.vs[0]);
+        }
       }
       P.ncomp = nc;
       P.hmax = P.hs[0];
@@ -910,10 +916,10 @@ int parse(const uint8_t *s, size_t n, Parsed &P, int frame, unsigned accept = 0)
 // script): afterwards P describes the frame as everything downstream of the
 // entropy decoder expects an interleaved baseline frame without restart
 // intervals, which is what the progressive kernels leave in the arena.
-int parse_progressive(const uint8_t *s, size_t n, Parsed &P, int frame) {
+int parse_progressive(const uint8_t *s, size_t n, Parsed &P, int frame, unsigned accept) {
   P = Parsed();
   auto F = std::make_shared<mij::ProgFrame>();
-  if (int rc = mij::prog_parse(s, n, *F, frame)) {
+  if (int rc = mij::prog_parse(s, n, *F, frame, (accept & MIJ_ACCEPT_440) != 0)) {
     memcpy(P.err, F->err, sizeof P.err);
     return rc;
   }
@@ -1456,7 +1462,7 @@ extern "C" int mij_decoder_decode(mij_decoder *d, const uint8_t *const *jpgs, co
         S.dc[i] = 4 * f + 2 * (P.interleaved ? P.td[c] : P.scan[k].td);
         S.ac[i] = 4 * f + 2 * (P.interleaved ? P.ta[c] : P.scan[k].ta) + 1;
         for (int y = 0; y < g.vs; y++)
-          for (int x = 0; x < g.hs; x++) {  // at most 2 * 2 + 1 + 1 = 6: parse() admits no other sampling
+          for (int x = 0; x < g.hs; x++) {  // at most 2 * 2 + 1 + 1 = 6: parse() admits no larger sampling
             S.slot_comp[S.bpm] = i;
             S.slot_x[S.bpm] = x;
             S.slot_y[S.bpm] = y;
@@ -1503,7 +1509,7 @@ extern "C" int mij_decoder_passes(mij_decoder *d) { return d ? d->last_passes : 
 extern "C" int mij_decoder_accept(mij_decoder *d, unsigned mask) {
   mij_clear_error();
   if (!d) return mij_fail(MIJ_EINVAL, "decoder_accept: null decoder");
-  if (mask & ~(unsigned)MIJ_ACCEPT_PROGRESSIVE) return mij_fail(MIJ_EINVAL, "decoder_accept: unknown bits in mask 0x%X", mask);
+  if (mask & ~(unsigned)(MIJ_ACCEPT_PROGRESSIVE | MIJ_ACCEPT_440)) return mij_fail(MIJ_EINVAL, "decoder_accept: unknown bits in mask 0x%X", mask);
   d->accept = mask;
   return MIJ_OK;
 }
@@ -1873,8 +1879,14 @@ struct XfPlan {
 
 // crop, then the edge rule, then the operation: decided from the markers
 // alone, before any device work.  MIJ_EINVAL names the frame and the reason.
+// accept: the decoder's MIJ_ACCEPT_* mask; with MIJ_ACCEPT_440 a transposing
+// operation on a frame with H != V swaps every component's H and V (4:2:2 <->
+// 4:4:0), which the decoder can then read back; without it
+// the operation is refused.  The crop, trim and whole-MCU rules below use the
+// source's MCU (Mw x Mh); the output's MCU is Mh x Mw after a transposition,
+// so X.mcus_x / _y, hence restart_rows, count the output's grid.
 static int xf_plan(const Parsed &P, int op, int flags, const area_t *crop, int restart_rows, const char *who,
-                   int frame, XfPlan &X) {
+                   int frame, XfPlan &X, unsigned accept = 0) {
   static const char *const names[mij::XF_OPS] = {"NONE",       "FLIP_H", "FLIP_V", "TRANSPOSE",
                                                  "TRANSVERSE", "ROT90",  "ROT180", "ROT270"};
   if (op < 0 || op >= mij::XF_OPS) return mij_fail(MIJ_EINVAL, "%s: frame %d: unknown operation %d", who, frame, op);
@@ -1893,7 +1905,7 @@ static int xf_plan(const Parsed &P, int op, int flags, const area_t *crop, int r
   }
   X.bits = mij::xf_op_bits(op);
   const bool T = X.bits & mij::XF_T;
-  if (T)
+  if (T && !(accept & MIJ_ACCEPT_440))
     for (int c = 0; c < P.ncomp; c++)
       if (P.hs[c] != P.vs[c])
         return mij_fail(MIJ_EINVAL, "%s: frame %d: %s of a component with sampling %dx%d: the transposed %dx%d is "
@@ -2446,7 +2458,7 @@ extern "C" int mij_decoder_transcode(mij_decoder *d, int restart_rows) {
   }
   std::vector<XfPlan> plans(n);
   for (int f = 0; f < n; f++)
-    if (int rc = xf_plan(d->parsed[f], MIJ_XF_NONE, 0, nullptr, restart_rows, "decoder_transcode", f, plans[f]))
+    if (int rc = xf_plan(d->parsed[f], MIJ_XF_NONE, 0, nullptr, restart_rows, "decoder_transcode", f, plans[f], d->accept))
       return rc;
   if (d->out_fmt == MIJ_OUT_PROGRESSIVE)
     for (int f = 0; f < n; f++)
@@ -2465,7 +2477,8 @@ extern "C" int mij_decoder_transform(mij_decoder *d, int op, int flags, const ar
   const int n = d->n;
   std::vector<XfPlan> plans(n);
   for (int f = 0; f < n; f++)
-    if (int rc = xf_plan(d->parsed[f], op, flags, crop, restart_rows, "decoder_transform", f, plans[f])) return rc;
+    if (int rc = xf_plan(d->parsed[f], op, flags, crop, restart_rows, "decoder_transform", f, plans[f], d->accept))
+      return rc;
   if (d->out_fmt == MIJ_OUT_PROGRESSIVE)
     for (int f = 0; f < n; f++)
       if (int rc = pw_check(d->parsed[f], plans[f], restart_rows, "decoder_transform", f)) return rc;

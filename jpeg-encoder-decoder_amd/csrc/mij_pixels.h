@@ -165,8 +165,22 @@ MIJ_HD void chroma10(const uint8_t *row, int c0, int cl, int cr, int v[10]) {
 // component's real size, ceil(w / 2) x ceil(h / 2) (downsampled_width /
 // _height), not of the padded plane; the "fancy" upsamplers only run when
 // that width is > 2, else each sample is replicated (jdsample.c).
+//
+// 4:4:0 (luma 1x2) is the transposed 4:2:2: chroma of the
+// frame's width and ceil(h / 2) rows, PIX_H1V2 (h1v2_fancy_upsample: each
+// sample with its upper or lower neighbour, no horizontal ones, hence no
+// small-width exception) or PIX_H1V2_REP (each row twice, at 1/8 scale).
 // ---------------------------------------------------------------------------
-enum { PIX_GREY = 0, PIX_444 = 1, PIX_H2V1 = 2, PIX_H2V1_REP = 3, PIX_H2V2 = 4, PIX_H2V2_REP = 5 };
+enum {
+  PIX_GREY = 0,
+  PIX_444 = 1,
+  PIX_H2V1 = 2,
+  PIX_H2V1_REP = 3,
+  PIX_H2V2 = 4,
+  PIX_H2V2_REP = 5,
+  PIX_H1V2 = 6,
+  PIX_H1V2_REP = 7
+};
 
 struct PixGeom {
   int w, h;         // the frame's real size
@@ -176,6 +190,7 @@ struct PixGeom {
   long long pitch;  // bytes between pixel rows: 3 * w rounded up to 16
 };
 
+// (the modes from PIX_H2V2 on are the two-row ones: a mode added after them must be one too, or this test changes)
 MIJ_HD int pix_rows_per_lane(int mode) { return mode >= PIX_H2V2 ? 2 : 1; }
 
 // 16 samples at columns x0 .. x0 + 15 (x0 % 16 == 0) of a padded row whose
@@ -216,6 +231,20 @@ MIJ_HD void replicate16(const int p[10], int out[16]) {
   for (int k = 0; k < 8; k++) out[2 * k] = out[2 * k + 1] = p[k + 1];
 }
 
+// jdsample.c h1v2_fancy_upsample: 16 samples of a chroma row (mid) and of its
+// upper and lower neighbours (the plane's edge rows replicated), four to a
+// word -> the two output rows they make
+MIJ_HD void upsample16_h1v2(const uint32_t mid[4], const uint32_t up[4], const uint32_t dn[4], int top[16],
+                            int bot[16]) {
+  MIJ_UNROLL
+  for (int p = 0; p < 16; p++) {
+    const int sh = 8 * (p & 3);
+    const int m = (int)((mid[p >> 2] >> sh) & 255);
+    top[p] = (3 * m + (int)((up[p >> 2] >> sh) & 255) + 1) >> 2;
+    bot[p] = (3 * m + (int)((dn[p >> 2] >> sh) & 255) + 2) >> 2;
+  }
+}
+
 // up to three aligned 16-byte stores of one output row's 16-pixel group; the
 // row is G.pitch bytes long (a multiple of 16), so a store that begins inside
 // it ends inside it.  Bytes between 3 * w and the pitch receive anything.
@@ -226,10 +255,18 @@ MIJ_HD void store_group(uint8_t *rowp, int g, long long pitch, const uint32_t wd
 }
 
 // Unit u, group g: output columns 16g .. 16g+15 of row u (one-row modes) or of
-// rows 2u and 2u+1 (h2v2 modes; the second only if < h).  g < ceil(w / 16),
-// u < h or ceil(h / 2).  Reads stay inside the padded planes (their rows are
-// yp / cp long and there are at least h, resp. ch, of them); stores stay
-// inside rows < h of the frame's pixel slot.
+// rows 2u and 2u+1 (h2v2 and h1v2 modes; the second only if < h).  g <
+// ceil(w / 16), u < h or ceil(h / 2).  Reads stay inside the padded planes
+// (their rows are yp / cp long and there are at least h, resp. ch, of them);
+// stores stay inside rows < h of the frame's pixel slot.
+//
+// The h1v2 modes: the chroma planes are as wide as the frame (cw == w <= cp, a
+// multiple of 8), so group g's row16 begins at byte 16g < w <= cp, its first 8
+// bytes end at 16g + 8 <= cp and its second 8 are loaded only if 16g + 8 <
+// cp: inside the row, as for luma.  The rows read are u and its neighbours
+// clamped to 0 .. ch - 1, with u < ceil(h / 2) == ch <= the padded plane's
+// rows.  Output rows 2u and 2u + 1 pass the same y < h test as the h2v2
+// modes' before their luma load and their stores.
 MIJ_HD void colour_tile_any(const uint8_t *Y, const uint8_t *Cb, const uint8_t *Cr, const PixGeom &G, int u, int g,
                             int rgb, uint8_t *pix) {
   const int nrows = pix_rows_per_lane(G.mode);
@@ -256,6 +293,18 @@ MIJ_HD void colour_tile_any(const uint8_t *Y, const uint8_t *Cb, const uint8_t *
     upsample16(mid, nb, crv[0]);
     chroma10_edge(Cr + (long long)rd * G.cp, 8 * g, G.cw, nb);
     upsample16(mid, nb, crv[1]);
+  } else if (G.mode == PIX_H1V2 || G.mode == PIX_H1V2_REP) {
+    // _REP: both neighbours are the row itself, (3 m + m + 1 or 2) >> 2 == m
+    const int ru = G.mode == PIX_H1V2 && u > 0 ? u - 1 : u, rd = G.mode == PIX_H1V2 && u + 1 < G.ch ? u + 1 : u;
+    uint32_t mid[4], up[4], dn[4];
+    row16(Cb + (long long)u * G.cp, 16 * g, G.cp, mid);
+    row16(Cb + (long long)ru * G.cp, 16 * g, G.cp, up);
+    row16(Cb + (long long)rd * G.cp, 16 * g, G.cp, dn);
+    upsample16_h1v2(mid, up, dn, cb[0], cb[1]);
+    row16(Cr + (long long)u * G.cp, 16 * g, G.cp, mid);
+    row16(Cr + (long long)ru * G.cp, 16 * g, G.cp, up);
+    row16(Cr + (long long)rd * G.cp, 16 * g, G.cp, dn);
+    upsample16_h1v2(mid, up, dn, crv[0], crv[1]);
   } else if (G.mode != PIX_GREY) {
     int p[10];
     chroma10_edge(Cb + (long long)u * G.cp, 8 * g, G.cw, p);
@@ -381,7 +430,8 @@ MIJ_HD uint32_t idct1_block(uint32_t dc, int32_t q0) {
 // component's IDCT size S starts at s and doubles while it stays <= 8 and
 // the component would otherwise be upsampled by a multiple of 2 both across
 // and down, so 4:2:0 chroma is scaled up inside its IDCT and needs no
-// upsampler, and 4:2:2 keeps its horizontal one.  Shared by the host
+// upsampler, 4:2:2 keeps its horizontal one and 4:4:0 its vertical one (fx ==
+// 1, fy == 2 at every scale).  Shared by the host
 // planner, the kernels' job tables and tests/scaled_check.cpp.
 struct ScaledComp {
   int S;       // the IDCT's output size: S x S samples per block
@@ -430,6 +480,7 @@ MIJ_HD void scaled_geometry(int w, int h, int ncomp, const int *hs, const int *v
   if (ncomp == 1) G.mode = PIX_GREY;
   else if (fx == 1 && fy == 1) G.mode = PIX_444;
   else if (fy == 1) G.mode = (G.c[1].cw > 2 && s > 1) ? PIX_H2V1 : PIX_H2V1_REP;  // libjpeg: no fancy upsampling at IDCT size 1
+  else if (fx == 1) G.mode = s > 1 ? PIX_H1V2 : PIX_H1V2_REP;  // (no small-width exception: no horizontal neighbours)
   else G.mode = (G.c[1].cw > 2 && s > 1) ? PIX_H2V2 : PIX_H2V2_REP;
 }
 

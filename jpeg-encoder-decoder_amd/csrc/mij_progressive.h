@@ -222,7 +222,8 @@ struct ProgFrame {
 };
 
 // 0, or 8 (MIJ_EJPEG) with the reason in F.err
-inline int prog_parse(const uint8_t *s, size_t n, ProgFrame &F, int frame) {
+// accept440: luma 1x2 is admitted too (MIJ_ACCEPT_440)
+inline int prog_parse(const uint8_t *s, size_t n, ProgFrame &F, int frame, bool accept440 = false) {
 #define PBAD(...)                                \
   do {                                           \
     snprintf(F.err, sizeof F.err, __VA_ARGS__);  \
@@ -299,8 +300,10 @@ inline int prog_parse(const uint8_t *s, size_t n, ProgFrame &F, int frame) {
       } else {
         if (F.hs[1] != 1 || F.vs[1] != 1 || F.hs[2] != 1 || F.vs[2] != 1)
           PBAD("stream %d: chroma sampling %dx%d / %dx%d (only 1x1)", frame, F.hs[1], F.vs[1], F.hs[2], F.vs[2]);
-        if (!(F.hs[0] <= 2 && F.vs[0] <= F.hs[0]))
+        if (!(F.hs[0] <= 2 && F.vs[0] <= F.hs[0]) && !(accept440 && F.hs[0] == 1 && F.vs[0] == 2)) {
+          if (accept440) PBAD("stream %d: luma sampling %dx%d (only 1x1, 2x1, 2x2, 1x2)", frame, F.hs[0], F.vs[0]);
           PBAD("stream %d: luma sampling %dx%d (only 1x1, 2x1, 2x2)", frame, F.hs[0], F.vs[0]);
+        }
       }
       F.ncomp = nc;
       F.hmax = F.hs[0];

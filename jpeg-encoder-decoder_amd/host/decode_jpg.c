@@ -11,11 +11,12 @@
  * With -scale 1/2, 1/4 or 1/8 the image comes out at that scale through
  * mij_decode_scaled, as djpeg -scale gives it (libjpeg's reduced IDCTs).
  *
- * With --progressive (first) progressive files are decoded too, through a
- * decoder object with MIJ_ACCEPT_PROGRESSIVE set (the one-shot calls refuse
- * them).
+ * With --progressive progressive files are decoded too, through a decoder
+ * object with MIJ_ACCEPT_PROGRESSIVE set (the one-shot calls refuse them).
+ * With --440 4:4:0 files, luma 1x2, are decoded too, the same way
+ * (MIJ_ACCEPT_440).  The options may come in any order.
  *
- *   decode_jpg [--progressive] [-scale 1/N] <in.jpg> <out.ppm>
+ *   decode_jpg [--progressive] [--440] [-scale 1/N] <in.jpg> <out.ppm>
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -42,24 +43,30 @@ static uint8_t *read_file(const char *path, size_t *len) {
 }
 
 int main(int argc, char **argv) {
-    int denom = 1, progressive = 0;
+    int denom = 1;
+    unsigned accept = 0;
     const char *prog = argv[0];
-    if (argc > 1 && !strcmp(argv[1], "--progressive")) {
-        progressive = 1;
-        argv++;
-        argc--;
-    }
-    if (argc == 5 && !strcmp(argv[1], "-scale")) {
-        char tail = 0;
-        if (sscanf(argv[2], "1/%d%c", &denom, &tail) != 1 || (denom != 1 && denom != 2 && denom != 4 && denom != 8)) {
-            fprintf(stderr, "%s: -scale %s: 1/1, 1/2, 1/4 or 1/8\n", prog, argv[2]);
-            return 2;
+    while (argc > 1 && argv[1][0] == '-' && argv[1][1]) {
+        int used = 1;
+        if (!strcmp(argv[1], "--progressive")) {
+            accept |= MIJ_ACCEPT_PROGRESSIVE;
+        } else if (!strcmp(argv[1], "--440")) {
+            accept |= MIJ_ACCEPT_440;
+        } else if (!strcmp(argv[1], "-scale") && argc > 2) {
+            char tail = 0;
+            if (sscanf(argv[2], "1/%d%c", &denom, &tail) != 1 || (denom != 1 && denom != 2 && denom != 4 && denom != 8)) {
+                fprintf(stderr, "%s: -scale %s: 1/1, 1/2, 1/4 or 1/8\n", prog, argv[2]);
+                return 2;
+            }
+            used = 2;
+        } else {
+            break;  /* the usage message below */
         }
-        argv += 2;
-        argc -= 2;
+        argv += used;
+        argc -= used;
     }
     if (argc != 3) {
-        fprintf(stderr, "usage: %s [--progressive] [-scale 1/N] <in.jpg> <out.ppm>\n", prog);
+        fprintf(stderr, "usage: %s [--progressive] [--440] [-scale 1/N] <in.jpg> <out.ppm>\n", prog);
         return 2;
     }
     size_t len = 0;
@@ -69,13 +76,13 @@ int main(int argc, char **argv) {
      * that reports the size and MIJ_ENOSPC before any device work */
     int w = 0, h = 0;
     uint8_t probe;
-    if (progressive) {
+    if (accept) {
         int fw = 16, fh = 16;
         mij_jpeg_size(jpg, len, &fw, &fh);
         mij_decoder *d = mij_decoder_create(0, fw < 16 ? 16 : (fw + 15) / 16 * 16, fh < 16 ? 16 : (fh + 15) / 16 * 16, 1);
         const uint8_t *streams[1] = {jpg};
         int lay[3 + 5 * 3];
-        int prc = d ? mij_decoder_accept(d, MIJ_ACCEPT_PROGRESSIVE) : mij_last_error();
+        int prc = d ? mij_decoder_accept(d, accept) : mij_last_error();
         if (!prc) prc = mij_decoder_decode(d, streams, &len, 1);
         if (!prc) prc = mij_decoder_reconstruct_scaled(d, MIJ_PIX_RGB, denom);
         if (!prc) prc = mij_decoder_scaled_layout(d, 0, denom, lay, 3 + 5 * 3);

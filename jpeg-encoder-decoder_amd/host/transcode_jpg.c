@@ -18,6 +18,9 @@
  *   -trim             cut a mirrored edge down to whole MCUs instead of refusing it
  *   --progressive     also take progressive files (MIJ_ACCEPT_PROGRESSIVE):
  *                     "progressive in, optimised baseline out"
+ *   --440             also take 4:4:0 files, luma 1x2 (MIJ_ACCEPT_440); a
+ *                     transposing operation then turns 4:2:2 into 4:4:0 and
+ *                     back instead of being refused
  *   --write-progressive   write a progressive file (jpegtran -progressive,
  *                     mij_decoder_output): libjpeg's ten-scan script, tables
  *                     optimised per scan; restart_rows counts rows of each
@@ -54,20 +57,27 @@ static int fail(const char *what, int rc) {
 }
 
 static int usage(const char *prog) {
-    fprintf(stderr, "usage: %s [--progressive] [--write-progressive] [-flip h|v] [-rotate 90|180|270] [-transpose] [-transverse] [-auto] [-trim]\n"
+    fprintf(stderr, "usage: %s [--progressive] [--440] [--write-progressive] [-flip h|v] [-rotate 90|180|270] [-transpose] [-transverse] [-auto] [-trim]\n"
             "       [-crop WxH+X+Y] <in.jpg> <out.jpg> [restart_rows]\n", prog);
     return 2;
 }
 
 int main(int argc, char **argv) {
     const char *prog = argv[0];
-    int op = MIJ_XF_NONE, flags = 0, have_crop = 0, have_xf = 0, automatic = 0, progressive = 0, write_progressive = 0;
+    int op = MIJ_XF_NONE, flags = 0, have_crop = 0, have_xf = 0, automatic = 0, write_progressive = 0;
+    unsigned accept = 0;
     area_t crop = {0, 0, 0, 0};
     while (argc > 1 && argv[1][0] == '-' && argv[1][1]) {
         const char *o = argv[1], *v = argc > 2 ? argv[2] : "";
         int used = 1;
         if (!strcmp(o, "--progressive")) {
-            progressive = 1;
+            accept |= MIJ_ACCEPT_PROGRESSIVE;
+            argc--;
+            argv++;
+            continue;
+        }
+        if (!strcmp(o, "--440")) {
+            accept |= MIJ_ACCEPT_440;
             argc--;
             argv++;
             continue;
@@ -110,7 +120,7 @@ int main(int argc, char **argv) {
     int w = 0, h = 0;
     uint8_t probe;
     int rc;
-    if (progressive) {  /* the one-shot calls refuse SOF2: the size from the frame header itself */
+    if (accept) {  /* the one-shot calls refuse SOF2 and luma 1x2: the size from the frame header itself */
         w = h = 16;
         mij_jpeg_size(jpg, len, &w, &h);
         if (w < 1) w = 1;
@@ -121,7 +131,7 @@ int main(int argc, char **argv) {
     }
     mij_decoder *d = mij_decoder_create(0, (w + 15) / 16 * 16, (h + 15) / 16 * 16, 1);
     if (!d) return fail("mij_decoder_create", mij_last_error());
-    if (progressive && (rc = mij_decoder_accept(d, MIJ_ACCEPT_PROGRESSIVE)) != MIJ_OK) return fail("mij_decoder_accept", rc);
+    if (accept && (rc = mij_decoder_accept(d, accept)) != MIJ_OK) return fail("mij_decoder_accept", rc);
     if (write_progressive && (rc = mij_decoder_output(d, MIJ_OUT_PROGRESSIVE)) != MIJ_OK) return fail("mij_decoder_output", rc);
     const uint8_t *streams[1] = {jpg};
     if ((rc = mij_decoder_decode(d, streams, &len, 1)) != MIJ_OK) return fail(argv[1], rc);

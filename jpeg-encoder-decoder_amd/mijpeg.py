@@ -1109,6 +1109,7 @@ def _order(order: str) -> int:
 
 
 ACCEPT_PROGRESSIVE = 1  # MIJ_ACCEPT_PROGRESSIVE
+ACCEPT_440 = 4  # MIJ_ACCEPT_440: luma 1x2; bit value 2 is unknown
 
 
 def jpeg_size(jpg: bytes):
@@ -1119,10 +1120,13 @@ def jpeg_size(jpg: bytes):
     return w.value, h.value
 
 
-def _progressive_decoder(jpg: bytes, progressive: bool = True, output: str = "baseline") -> "Decoder":
-    """a decoder of the stream's size with MIJ_ACCEPT_PROGRESSIVE set (or not), holding the decoded stream"""
+def _progressive_decoder(jpg: bytes, progressive: bool = True, output: str = "baseline",
+                         accept440: bool = False) -> "Decoder":
+    """a decoder of the stream's size with MIJ_ACCEPT_PROGRESSIVE and MIJ_ACCEPT_440 set (or not), holding the
+    decoded stream"""
     w, h = jpeg_size(jpg)  # (0, 0): the decoder then says what is wrong
-    d = Decoder(max(16, (w + 15) // 16 * 16), max(16, (h + 15) // 16 * 16), 1, progressive=progressive)
+    d = Decoder(max(16, (w + 15) // 16 * 16), max(16, (h + 15) // 16 * 16), 1, progressive=progressive,
+                accept440=accept440)
     try:
         d.output(output)
         d.decode([jpg])
@@ -1132,13 +1136,15 @@ def _progressive_decoder(jpg: bytes, progressive: bool = True, output: str = "ba
     return d
 
 
-def decode(jpg: bytes, order: str = "bgr", scale: int = 1, progressive: bool = False) -> np.ndarray:
+def decode(jpg: bytes, order: str = "bgr", scale: int = 1, progressive: bool = False,
+           accept440: bool = False) -> np.ndarray:
     """mij_decode: one baseline JFIF stream -> (h, w, 3) uint8 pixels, host to
     host; scale = 2, 4, 8: mij_decode_scaled, the image at 1/scale as
     libjpeg's reduced IDCTs give it.  progressive=True: through
-    a Decoder that also accepts progressive streams."""
-    if progressive:
-        d = _progressive_decoder(jpg)
+    a Decoder that also accepts progressive streams (DESIGN.md §4p);
+    accept440=True: through one that also accepts 4:4:0."""
+    if progressive or accept440:
+        d = _progressive_decoder(jpg, progressive, accept440=accept440)
         try:
             d.reconstruct(order, scale)
             return d.pixels(0)
@@ -1169,15 +1175,17 @@ def decode(jpg: bytes, order: str = "bgr", scale: int = 1, progressive: bool = F
 OUTPUTS = {"baseline": 0, "progressive": 1}
 
 
-def transcode(jpg: bytes, restart_rows: int = 0, progressive: bool = False, output: str = "baseline") -> bytes:
+def transcode(jpg: bytes, restart_rows: int = 0, progressive: bool = False, output: str = "baseline",
+              accept440: bool = False) -> bytes:
     """mij_transcode: one baseline stream -> the same coefficients in one
     interleaved scan with optimised Huffman tables and restart intervals of
     restart_rows MCU rows (0: none), host to host; lossless.
     progressive=True: through a Decoder that also accepts progressive streams
     ("progressive in, optimised baseline out").  output="progressive": the
-    same coefficients as a progressive file instead."""
-    if progressive or output != "baseline":
-        d = _progressive_decoder(jpg, progressive, output)
+    same coefficients as a progressive file instead.
+    accept440=True: through a Decoder that also accepts 4:4:0."""
+    if progressive or accept440 or output != "baseline":
+        d = _progressive_decoder(jpg, progressive, output, accept440)
         try:
             d.transcode(restart_rows)
             return d.transcoded(0)
@@ -1228,17 +1236,19 @@ def _xf_args(jpg, op, trim, crop):
 
 
 def transform(jpg: bytes, op="rot90", trim: bool = False, crop=None, restart_rows: int = 0,
-              progressive: bool = False, output: str = "baseline") -> bytes:
+              progressive: bool = False, output: str = "baseline", accept440: bool = False) -> bytes:
     """mij_transform: one baseline stream -> the flipped / transposed / rotated
     (op, by name; "auto": by the stream's EXIF orientation) and / or cropped
     (crop = (x, y, w, h), MCU-aligned offset) image, coded as transcode codes
     it; lossless.  trim: cut a mirrored dimension down to
     whole MCUs instead of refusing it.  progressive=True: through a Decoder
     that also accepts progressive streams.  output="progressive": written
-    as a progressive file."""
-    if progressive or output != "baseline":
+    as a progressive file.  accept440=True: through a Decoder
+    that also accepts 4:4:0, with which a transposing operation turns 4:2:2
+    into 4:4:0 and back instead of being refused."""
+    if progressive or accept440 or output != "baseline":
         code, _, _ = _xf_args(jpg, op, trim, crop)  # resolves "auto" from the stream
-        d = _progressive_decoder(jpg, progressive, output)
+        d = _progressive_decoder(jpg, progressive, output, accept440)
         try:
             d.transform(code, trim, crop, restart_rows)
             return d.transcoded(0)
@@ -1262,20 +1272,23 @@ class Decoder:
     libjpeg writes: one interleaved scan, greyscale / 4:4:4 / 4:2:2 / 4:2:0,
     any size, restart intervals) -> coefficient planes, entropy-decoded on
     the GPU, and from those (reconstruct) the pixels libjpeg would give.
-    progressive=True (mij_decoder_accept): progressive streams too."""
+    progressive=True (mij_decoder_accept): progressive streams too;
+    accept440=True: 4:4:0 too, and transposing transforms of 4:2:2."""
 
-    def __init__(self, max_w: int, max_h: int, max_frames: int, device: int = 0, progressive: bool = False):
+    def __init__(self, max_w: int, max_h: int, max_frames: int, device: int = 0, progressive: bool = False,
+                 accept440: bool = False):
         self.lib = load()
         self.scale_ = 1  # of the last reconstruct
         self.h_ = self.lib.mij_decoder_create(device, max_w, max_h, max_frames)
         if not self.h_:
             raise MijError("mij_decoder_create failed: "
                            f"{self.lib.mij_strerror(self.lib.mij_last_error()).decode()}")
-        if progressive:
-            self.accept(ACCEPT_PROGRESSIVE)
+        if progressive or accept440:
+            self.accept((ACCEPT_PROGRESSIVE if progressive else 0) | (ACCEPT_440 if accept440 else 0))
 
     def accept(self, mask: int) -> None:
-        """mij_decoder_accept: what the decoder takes beyond baseline (ACCEPT_PROGRESSIVE), until changed"""
+        """mij_decoder_accept: what the decoder takes beyond baseline (ACCEPT_PROGRESSIVE | ACCEPT_440), until
+        changed"""
         _check(self.lib.mij_decoder_accept(self.h_, mask), "decoder_accept")
 
     def output(self, fmt: str) -> None:
@@ -1515,18 +1528,50 @@ def resize(frame: np.ndarray, size, filter="bicubic") -> np.ndarray:
 
 
 def thumbnail(jpg: bytes, size, filter="bicubic", quality: int = 75, arithmetic: str = "reference",
-              sampling: str = "420") -> bytes:
+              sampling: str = "420", accept440: bool = False) -> bytes:
     """mij_thumbnail: one baseline stream -> a JPEG of exactly size = (w, h):
     decoded at thumbnail_denom, resized, encoded as encode_any encodes; the
     pixels never leave the device.  arithmetic "libjpeg": through
     mij_thumbnail_libjpeg at `sampling`, the coefficients Pillow's draft ->
     resize -> save(quality, subsampling) gives; with the
-    default arithmetic the sampling is 4:2:0 and nothing else."""
+    default arithmetic the sampling is 4:2:0 and nothing else.
+    accept440=True: the same three stages on one stream through a Decoder
+    that also accepts 4:4:0."""
     lib = load()
     buf = np.frombuffer(jpg, np.uint8)
     ow, oh = int(size[0]), int(size[1])
     n = C.c_size_t(0)
     samp = _sampling(sampling)
+    if accept440:
+        if samp and not _arithmetic(arithmetic):
+            raise ValueError(f"thumbnail: sampling {sampling!r} needs arithmetic=\"libjpeg\"")
+        if ow < 1 or oh < 1 or ow > 65535 or oh > 65535:
+            raise MijError(f"thumbnail: out size {ow}x{oh} (1..65535 each)")
+        d = _progressive_decoder(jpg, False, accept440=True)
+        r = b = None
+        try:
+            w, h, _ = d.info(0)
+            denom = thumbnail_denom(w, h, ow, oh)
+            r = Resizer(1)
+            b = Batch((ow + 15) // 16 * 16, (oh + 15) // 16 * 16, 1, int(quality))
+            r.set_stream(d.stream_ptr())
+            b.set_stream(d.stream_ptr())
+            d.reconstruct("bgr", denom)
+            ptr, pitch = d.device_pixels(0)
+            r.resize([(ptr, pitch, -(-w // denom), -(-h // denom))], [(ow, oh)], filter)
+            ptr, pitch = r.device_pixels(0)
+            b.pad_input(ptr, 0, pitch, [(ow, oh)])
+            if _arithmetic(arithmetic):
+                b.encode_libjpeg(1, sampling)
+            else:
+                b.encode_interleaved(1)
+            return b.output(0)
+        finally:  # the borrowers of the decoder's stream first
+            if b is not None:
+                b.close()
+            if r is not None:
+                r.close()
+            d.close()
     if _arithmetic(arithmetic):
         out = np.zeros(max(int(lib.mij_max_jpg_bytes_sampled(ow, oh, samp, 0)), 1), np.uint8)
         _check(lib.mij_thumbnail_libjpeg(_ptr(buf), buf.size, ow, oh, _filter(filter), int(quality), samp, _ptr(out),
@@ -1746,7 +1791,8 @@ class Loader:
     """Stored JPEGs -> one normalised tensor on the device (mij_loader_*):
     decode at a scale, crop, resize, tensorize, on one stream."""
 
-    def __init__(self, max_w: int, max_h: int, max_frames: int, device: int = 0, progressive: bool = False):
+    def __init__(self, max_w: int, max_h: int, max_frames: int, device: int = 0, progressive: bool = False,
+                 accept440: bool = False):
         self.lib = load()
         self.last_ = None
         self.h_ = self.lib.mij_loader_create(device, max_w, max_h, max_frames)
@@ -1754,8 +1800,8 @@ class Loader:
             raise MijError("mij_loader_create failed: "
                            f"{self.lib.mij_strerror(self.lib.mij_last_error()).decode()}: "
                            f"{self.lib.mij_last_message().decode(errors='replace')}")
-        if progressive:
-            self.accept(ACCEPT_PROGRESSIVE)
+        if progressive or accept440:
+            self.accept((ACCEPT_PROGRESSIVE if progressive else 0) | (ACCEPT_440 if accept440 else 0))
 
     def accept(self, mask: int) -> None:
         """mij_loader_accept: as Decoder.accept, for the loader's decoder"""
